@@ -31,6 +31,12 @@ link once), where h = a*b - c and the h-slice MSM are computed.
 
 Prints ONE JSON line (rank 0).  `roofline` = dominant kernel (G1 bucket accumulation) against the HBM peak, measured live
 with HIP events on the kernels' own stream; `cpu_baseline` = the oracle's C++ restatement of the same workload on the host.
+
+A plain N = 1 run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it opens the session, warms up, times
+K proofs through the entry and prints the line.  `--full` adds everything else above: the resident step with its isolated launches,
+rooflines and copy ceiling, the entry's extras, `sizes`, the Poseidon fixture, the second curve, the in-run counter passes and
+`cpu_baseline`.  `--dump-outputs DIR` writes the last timed proof (or, when the resident step is the headline, its folded MSM results)
+as float64 .npy files; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import importlib
@@ -462,11 +468,13 @@ def compact_line(out, detail_path):
     line["value_basis"] = basis.split(":")[0].split(" — ")[0][:160]
     line["rccl_ranks_seen"] = out.get("rccl_ranks_seen")
     rf = out.get("roofline") or {}
-    line["roofline"] = pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "algorithmic_bytes_per_launch", "measured_copy_ceiling_GBs"))
-    line["roofline"]["traffic"] = rf.get("traffic")       # null stays on the line
-    line["roofline"]["kernel"] = (rf.get("kernel") or "").split(" (")[0]
+    if rf:                                                # (a plain N = 1 run has the headline only: rooflines come with --full)
+        line["roofline"] = pick(rf, ("bound", "achieved", "peak", "unit", "frac", "traffic", "launch_ms", "algorithmic_bytes_per_launch", "measured_copy_ceiling_GBs"))
+        line["roofline"]["traffic"] = rf.get("traffic")   # null stays on the line
+        line["roofline"]["kernel"] = (rf.get("kernel") or "").split(" (")[0]
     vr = out.get("valu_roofline") or {}
-    line["valu_roofline"] = pick(vr, ("achieved", "peak", "frac", "unit"))
+    if vr:
+        line["valu_roofline"] = pick(vr, ("achieved", "peak", "frac", "unit"))
     for name in ("roofline_g2", "roofline_ntt"):
         if out.get(name):
             line[name] = pick(out[name], ("achieved", "frac", "launch_ms"))
@@ -479,7 +487,8 @@ def compact_line(out, detail_path):
             if isinstance(cb.get(twin), dict):
                 line["cpu_baseline"][twin] = pick(cb[twin], ("value", "unit", "cores", "ms_per_proof", "seconds", "kind", "error"))
     sr = out.get("step_resident") or {}
-    line["step_resident"] = pick(sr, ("value", "unit", "ms_per_step"))
+    if sr:
+        line["step_resident"] = pick(sr, ("value", "unit", "ms_per_step"))
     pe = out.get("product_entry") or {}
     if pe:
         line["product_entry"] = pick(pe, ("ms_per_proof", "ms_per_proof_min_inner", "value", "proofs", "three_parties_agree", "plain_driver_ms", "error", "devices"))
@@ -534,6 +543,15 @@ def emit(out, detail_path=None):
     sys.stdout.flush()
 
 
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: uint64 limb arrays -> DIR/<name>.npy as float64, each limb split into its two 32-bit words (low word first), which
+    float64 holds exactly"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        np.save(os.path.join(dirname, name + ".npy"), a.view(np.uint32).reshape(a.shape[:-1] + (2 * a.shape[-1],)).astype(np.float64))
+
+
 def cpu_baseline(log_m_target=22, threads_cap=None, budget_s=45.0):
     """oracle (C++ restatement of the reference path, arkworks' algorithms) timed on this host's cores on the SAME workload as the GPU
     line when the host manages it within the budget (2 x EPYC 9575F: 2^22 in ~35 s), else on the largest smaller domain that does.
@@ -586,7 +604,7 @@ def cpu_baseline(log_m_target=22, threads_cap=None, budget_s=45.0):
                            "note": "same inputs; " + ("both settings cover all 15 MSM windows, so the MSM stage times are shared and only the other stages were re-timed" if shared else "full second run")}}
 
 
-def entry_leg(ctx, log_m, device, proofs, warmup, curve=None, extras=True, barrier=None, devices=None, files=None):
+def entry_leg(ctx, log_m, device, proofs, warmup, curve=None, extras=True, barrier=None, devices=None, files=None, outputs=None):
     """The product's entry under the driver's clock — what co-circom.rs:503-506 times: a proving session on a zkey FILE (product-side
     synthetic circuit with a valid CRS, cgh_synth_circuit) and ONE REP3 party through cgh_session_prove_rep3_party_ex, the entry the CLI
     patch binds.  Host buffers in, proof out: witness shares cross PCIe, the masks of both mul_vec calls are drawn INSIDE the call on the
@@ -597,7 +615,8 @@ def entry_leg(ctx, log_m, device, proofs, warmup, curve=None, extras=True, barri
     pre-drawn masks, the Shamir twin.  devices: the party's GPUs — the session is then opened with cgh_session_open_multi over them (the product's
     multi-GPU path, SURVEY.md §8e: table slices per device, witness map distributed, partial sums folded on the host).  files = (zkey, wtns):
     an existing circuit instead of the synthetic one (log_m is then read from the zkey) — the reference's own bench circuit, Poseidon(2),
-    tests/benches/poseidon_hash2.rs:175-223, is the fixture tests/golden/groth16/bn254/poseidon."""
+    tests/benches/poseidon_hash2.rs:175-223, is the fixture tests/golden/groth16/bn254/poseidon.  outputs (a dict): receives the last
+    timed proof as "proof" (8 x words-per-field-element uint64: A, B, C affine)."""
     import shutil
     import tempfile
     import threading
@@ -693,6 +712,8 @@ def entry_leg(ctx, log_m, device, proofs, warmup, curve=None, extras=True, barri
         for rnd_, _ in prepared: rnd_.close()
         if not all((got == proofs3[0]).all() for got, _ in timed): raise RuntimeError("the party served its recorded traffic produced a different proof")
         inner = [sec for _, sec in timed]
+        if outputs is not None:
+            outputs["proof"] = timed[-1][0].copy()
         out.update({"proofs": proofs, "warmup": warmup, "elapsed_s": elapsed, "ms_per_proof": elapsed / proofs * 1e3, "ms_per_proof_min_inner": min(inner) * 1e3, "ms_per_proof_mean_inner": sum(inner) / len(inner) * 1e3, "ms_inner_each": [round(x * 1e3, 1) for x in inner],
                     "value": nc / (elapsed / proofs), "unit": "constraints/s"})
         if extras:
@@ -979,6 +1000,12 @@ def main():
                     "one rank on, so that a single GPU drives the RCCL all_to_all / all_gather / all_reduce calls of the N >= 4 path")
     ap.add_argument("--one-context", action="store_true", help="run the aux-witness MSMs after the witness map on the same context (no overlap)")
     ap.add_argument("--precompute", type=int, default=-1, help="window size of the per-window precomputed base tables (-1 = by table size: 20 above ~3 M G1 / ~1.5 M G2 points else 17; 0 = off)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline: for N = 1 the resident step with its isolated launches, rooflines and copy "
+                    "ceiling, the entry's extras (host draws, plain driver, Shamir twin), the `sizes` legs, the Poseidon fixture, the second curve, the in-run "
+                    "counter passes and the CPU baseline (--no-sizes / --no-cpu-baseline still drop theirs).  Without it an N = 1 run times the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the timed path handed its caller in the last step "
+                    "as DIR/<name>.npy, float64: the proof's affine points A, B, C of the entry (or the folded MSM results of the resident step when that "
+                    "is the headline), each 64-bit limb split into two 32-bit words, low word first")
     args = ap.parse_args()
     global CURVE
     CURVE = cg.BN254 if args.curve == "bn254" else cg.BLS12_381
@@ -989,18 +1016,22 @@ def main():
     if args.emulate:
         emulate = tuple(int(x) for x in args.emulate.split(":"))
     # `python bench.py --gpus N` with no launcher around it (the driver's N = 1 command shape): start the N ranks here, one per GPU, under
-    # torch.distributed.run — and refuse loudly when the box has fewer GPUs than ranks (test mode --shared-device puts every rank on GPU 0)
+    # torch.distributed.run — and refuse loudly when the box has fewer GPUs than ranks (test mode --shared-device puts every rank on GPU 0).
+    # The launcher is a child process: this process has already opened the GPU (the checks above), and replacing such a process with
+    # exec is not safe on every driver.
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not emulate:
         have = torch.cuda.device_count()
         if have < args.gpus and not args.shared_device:
             raise SystemExit(f"bench.py --gpus {args.gpus}: only {have} GPU(s) visible (one rank per GPU; --shared-device --backend gloo is the one-GPU test mode)")
         import socket
+        import subprocess
         with socket.socket() as sock:
             sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         sys.stdout.flush(); sys.stderr.flush()
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
-                                  "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
+                            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:])
+        sys.exit(p.returncode if p.returncode >= 0 else 128 - p.returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1060,30 +1091,37 @@ def main():
     ctx.set_stream(stream.cuda_stream)
     torch.cuda.set_stream(stream)
     ctx.set_scatter_capacity(args.scatter_cap)
-    w = Workload(ctx, args.log_m, device, emulate[1] if emulate else rank, emulate[0] if emulate else world, precompute=args.precompute)
-    w.emulate = emulate is not None
-    w.g2_last = args.g2_last
-    w.comm = comm
-    w.pcie = None
-    if args.pcie:
-        pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory().copy_(t.cpu())
-        w.pcie = {"up": [(getattr(w, k), pin(getattr(w, k))) for k in ("wa", "wb", "mask1", "mask2", "recv1", "recv2")],
-                  "down": [(getattr(w, k), pin(getattr(w, k))) for k in ("ca", "ha")]}
-    w.ctx_aux = None
-    if not args.one_context:
-        w.ctx_aux = cg.Context(local_rank)
-        w.ctx_aux.set_scatter_capacity(args.scatter_cap)
+    # The inputs-resident step: the headline with --no-session, the strong-scaling figure of N > 1, and what the resident-step options act on.
+    # A plain N = 1 run leads with the product entry and leaves it to --full.
+    resident = (args.full or args.no_session or world > 1 or emulate is not None or args.force_dist or args.one_context or args.g2_last or args.pcie
+                or bool(args.soak) or args.dump_result is not None)
+    w = None
+    if resident:
+        w = Workload(ctx, args.log_m, device, emulate[1] if emulate else rank, emulate[0] if emulate else world, precompute=args.precompute)
+        w.emulate = emulate is not None
+        w.g2_last = args.g2_last
+        w.comm = comm
+        w.pcie = None
+        if args.pcie:
+            pin = lambda t: torch.empty(t.shape, dtype=t.dtype).pin_memory().copy_(t.cpu())
+            w.pcie = {"up": [(getattr(w, k), pin(getattr(w, k))) for k in ("wa", "wb", "mask1", "mask2", "recv1", "recv2")],
+                      "down": [(getattr(w, k), pin(getattr(w, k))) for k in ("ca", "ha")]}
+        w.ctx_aux = None
+        if not args.one_context:
+            w.ctx_aux = cg.Context(local_rank)
+            w.ctx_aux.set_scatter_capacity(args.scatter_cap)
     torch.cuda.synchronize()
 
     def barrier():
         torch.cuda.synchronize(); ctx.sync()
-        if w.ctx_aux is not None:
+        if w is not None and w.ctx_aux is not None:
             w.ctx_aux.sync()
         if dist is not None:
             dist.barrier()
 
-    run_step = (lambda: step(w)) if emulate else (lambda: exchange(step(w), w.plan, comm, CURVE))
-    elapsed, st, res = timed_resident_steps(w, [c for c in (ctx, w.ctx_aux) if c is not None], args.steps, args.warmup, run_step, barrier, comm)
+    if resident:
+        run_step = (lambda: step(w)) if emulate else (lambda: exchange(step(w), w.plan, comm, CURVE))
+        elapsed, st, res = timed_resident_steps(w, [c for c in (ctx, w.ctx_aux) if c is not None], args.steps, args.warmup, run_step, barrier, comm)
 
     if args.soak and not emulate:
         ref = {t: np.array(v, copy=True) for t, v in res.items()}
@@ -1100,11 +1138,14 @@ def main():
             print(f"soak: {args.soak} extra steps reproduced the results bit for bit", file=sys.stderr)
 
     single = rank == 0 and not emulate and world == 1
-    iso = isolated_kernels(w, ctx, barrier) if single else None
-    g1_pts = [hi - lo for (t, i, parts), (b, lo, hi) in w.tables.items() if TABLE_GROUP[t] == 0]
+    iso = isolated_kernels(w, ctx, barrier) if single and args.full else None
+    g1_pts = [hi - lo for (t, i, parts), (b, lo, hi) in w.tables.items() if TABLE_GROUP[t] == 0] if resident else []
+    folded = None                                      # the resident step's results as its caller gets them: affine points, table -> (2 components, words)
+    if resident and rank == 0 and not emulate:
+        folded = {t: np.stack([cg.point_to_affine(CURVE, cg.G1 if TABLE_GROUP[t] == 0 else cg.G2, res[t][j]) for j in range(2)]) for t in TABLES}
 
     if rank == 0 and args.dump_result:
-        dump = {t: np.stack([cg.point_to_affine(CURVE, cg.G1 if TABLE_GROUP[t] == 0 else cg.G2, res[t][j]) for j in range(2)]) for t in TABLES}
+        dump = dict(folded)
         if args.dump_inputs:
             u64 = lambda t: t.cpu().numpy().view(np.uint64) if t.dtype == torch.int64 else t.cpu().numpy()
             for name in ("rpA", "colA", "coA", "rpB", "colB", "coB", "pub", "wa", "wb", "mask1", "mask2", "recv1", "recv2"):
@@ -1120,6 +1161,7 @@ def main():
     # (cgh_session_open_multi: one process drives the party's devices, as one `co-circom` process would).  Rank 0 is that process; the
     # other ranks have done their part in the resident leg above and wait in a HOST-side barrier, their GPUs free for the session.
     multi_ent = None
+    entry_out = {}                                     # the headline entry's last timed proof (entry_leg's `outputs`)
     if world > 1 and not emulate and not args.no_session:
         w.release()
         for c in (w.ctx_aux, ctx):                    # the waiting ranks give their contexts back: rank 0's session is alone on the job's GPUs
@@ -1130,11 +1172,11 @@ def main():
         if rank == 0:
             devs = [0] * world if args.shared_device else list(range(world))
             try:
-                multi_ent = entry_leg(ctx, args.log_m, device, args.steps, args.warmup, CURVE, extras=False, devices=devs)
+                multi_ent = entry_leg(ctx, args.log_m, device, args.steps, args.warmup, CURVE, extras=False, devices=devs, outputs=entry_out)
             except Exception as e:                                                       # noqa: BLE001 (the line survives: `value` stays the resident step and says so)
                 multi_ent = {"error": f"{type(e).__name__}: {e}"[:400], "devices": devs}
         host_barrier()
-    if rank == 0:
+    if rank == 0 and resident:
         step_ms = elapsed / args.steps * 1e3
         step_value = w.nc / (elapsed / args.steps)
         ptb = G1_POINT_BYTES[CURVE]
@@ -1160,18 +1202,19 @@ def main():
         # "state the measured stream-copy ceiling beside" the 8 TB/s peak: one 1 GiB device-to-device copy (read + write),
         # best of 5, timed with events on the stream the copy runs on (torch's current stream)
         copy_gbs = None
-        try:
-            src = torch.empty(1 << 30, dtype=torch.uint8, device=device); dst = torch.empty_like(src)
-            dst.copy_(src); torch.cuda.synchronize(device)
-            best = None
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); dst.copy_(src); e1.record(); torch.cuda.synchronize(device)
-                t = e0.elapsed_time(e1); best = t if best is None else min(best, t)
-            copy_gbs = 2.0 * (1 << 30) / (best * 1e-3) / 1e9
-            del src, dst
-        except Exception:                                                                # noqa: BLE001 (a side figure)
-            copy_gbs = None
+        if args.full:
+            try:
+                src = torch.empty(1 << 30, dtype=torch.uint8, device=device); dst = torch.empty_like(src)
+                dst.copy_(src); torch.cuda.synchronize(device)
+                best = None
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(); dst.copy_(src); e1.record(); torch.cuda.synchronize(device)
+                    t = e0.elapsed_time(e1); best = t if best is None else min(best, t)
+                copy_gbs = 2.0 * (1 << 30) / (best * 1e-3) / 1e9
+                del src, dst
+            except Exception:                                                            # noqa: BLE001 (a side figure)
+                copy_gbs = None
         free_b, total_b = torch.cuda.mem_get_info(device)
         acc_bytes = (ptb + 32.0) * iso_pts
         achieved = (acc_bytes / (iso_ms * 1e-3) / 1e9) if iso_ms else ((ptb + 32.0) * avg_pts / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0)
@@ -1236,13 +1279,28 @@ def main():
                                           "mask draws, mul_vec exchanges over PCIe and the host steps inside the timed call; step_resident = the per-rank resident scaling of the same proof's kernels (one process per GPU over RCCL)")
                 else:
                     out["value_basis"] = "step_resident (inputs resident in HBM): the multi-device product entry FAILED on this box (product_entry.error), so this line is NOT on the N = 1 line's basis — compare with step_resident.value there"
+    elif rank == 0:
+        # a plain N = 1 run: the headline alone, filled in by the entry leg below
+        cname = CURVE_NAME[CURVE]
+        m_ = 1 << args.log_m
+        out = {
+            "metric": f"Groth16 constraints/sec ({cname}, 2^{args.log_m} R1CS), one REP3 party's prove",
+            "value": None, "unit": "constraints/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": None, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "rccl_ranks_seen": ranks_seen, "backend": (args.backend if dist is not None else None),
+            "dtype": "u32 limbs (%d-bit modular integer arithmetic)" % FR[CURVE][2], "data": "synthetic",
+            "config": {"workload": f"synthetic R1CS 2^{args.log_m} constraints-domain {cname}, REP3 co-groth16 (configs[2])",
+                       "num_constraints": m_ - 2, "domain_size": m_, "n_vars": m_, "nnz": 3 * (m_ - 2), "share_components": 2,
+                       "msm": "8 G1 + 2 G2 of ~2^%d points" % args.log_m, "ntt": 12},
+        }
+    if rank == 0:
         legs = not args.no_session and world == 1
 
         def entry_alone(*a, **kw):
             """An entry leg with the harness's second context closed: that context belongs to the resident legs, and its idle streams would sit on
             hardware queues next to the session's own (a 2^16 party as a leg of this process: 3.8 ms with it open, 3.2 in a process that holds
             only the session, scripts/later_leg.py).  The resident legs get a new one afterwards."""
-            had = w.ctx_aux is not None
+            had = w is not None and w.ctx_aux is not None
             if had:
                 w.ctx_aux.sync(); w.ctx_aux.close(); w.ctx_aux = None
             try:
@@ -1251,18 +1309,27 @@ def main():
                 if had:
                     w.ctx_aux = cg.Context(local_rank); w.ctx_aux.set_scatter_capacity(args.scatter_cap)
         if legs:
-            w.release()                                                 # the session registers its own tables (another 21 GB of window copies at 2^22)
+            if w is not None:
+                w.release()                                             # the session registers its own tables (another 21 GB of window copies at 2^22)
             try:
-                ent = entry_alone(ctx, args.log_m, device, args.steps, args.warmup, CURVE, extras=True)
+                ent = entry_alone(ctx, args.log_m, device, args.steps, args.warmup, CURVE, extras=args.full, outputs=entry_out)
                 # THE HEADLINE: the reference's timed region through the product's entry
                 out["value"], out["ms_per_step"] = ent["value"], ent["ms_per_proof"]
                 out["value_basis"] = ("product entry: ONE REP3 party through cgh_session_prove_rep3_party_ex — witness shares in host memory in, proof out, the party's ChaCha12 mask draws, both "
                                       "mul_vec exchanges over PCIe and the O(1) host steps inside the timed call (co-circom.rs:503-506); `steps` = proofs between the two barriers. "
-                                      "step_resident holds the inputs-resident kernel pipeline (the bench contract's HBM-resident figure)")
+                                      "step_resident (--full) holds the inputs-resident kernel pipeline (the bench contract's HBM-resident figure)")
                 out["product_entry"] = ent
             except Exception as e:                                      # the contract line must survive a failing leg; the failure is on the line and `value` stays the resident step
+                if not resident:
+                    raise                                               # no resident step to fall back on: a line without its headline is an error
                 out["product_entry"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-        if legs and not args.no_sizes:
+        if args.dump_outputs:
+            if "proof" in entry_out and "value" in out.get("product_entry", {}):
+                p_ = entry_out["proof"]; q = p_.shape[0] // 8             # A (G1), B (G2), C (G1), affine
+                dump_outputs(args.dump_outputs, {"proof_a": p_[:2 * q], "proof_b": p_[2 * q:6 * q], "proof_c": p_[6 * q:]})
+            else:
+                dump_outputs(args.dump_outputs, {"msm_" + t: v for t, v in folded.items()})
+        if args.full and legs and not args.no_sizes:
             sizes = {}
             for lg in [int(x) for x in args.sizes.split(",") if x]:
                 if lg == args.log_m:
@@ -1296,7 +1363,7 @@ def main():
                     "roofline": r_["roofline"], "roofline_g2": r_["roofline_g2"], "roofline_ntt": r_["roofline_ntt"], "valu_roofline": r_["valu_roofline"], "isolated_ms": r_["isolated_ms"], "stages": r_["stages"]}
             except Exception as e:                                      # noqa: BLE001
                 out.setdefault("session", {})["bls12_381" if CURVE == cg.BN254 else "bn254"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-        if world == 1 and CURVE == cg.BN254 and not args.no_session:
+        if args.full and world == 1 and CURVE == cg.BN254 and not args.no_session:
             try:
                 w.release()
             except Exception:                                                                # noqa: BLE001
@@ -1306,7 +1373,7 @@ def main():
                 out["roofline"]["traffic"] = measured; out["roofline"]["traffic_note"] = why
             else:
                 out["roofline"]["traffic_note"] += "; in-run measurement: " + why
-        if not args.no_cpu_baseline and world == 1 and CURVE == cg.BN254:
+        if args.full and not args.no_cpu_baseline and world == 1 and CURVE == cg.BN254:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.log_m)
             except Exception as e:

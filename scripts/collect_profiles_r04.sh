@@ -11,11 +11,11 @@ rm -rf $O; mkdir -p $O
 cd $R
 if [ "${SKIP_TESTS:-0}" != "1" ]; then timeout 2700 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.txt 2>&1; fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
-timeout 900 python bench.py --curve bls12_381 --steps 10 --warmup 3 --no-sizes --no-cpu-baseline > $O/bench_bls.json 2> $O/bench_bls.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --curve bls12_381 --steps 10 --warmup 3 --no-sizes --no-cpu-baseline > $O/bench_bls.json 2> $O/bench_bls.err
 timeout 400 python scripts/fuzz_msm.py 300 11 > $O/fuzz_msm.txt 2>&1
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-session > $O/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-session > $O/stats.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python $R/scripts/serial_kernels.py 22 5 > $O/serial.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial_bls -- python $R/scripts/serial_kernels.py 22 3 bls12_381 > $O/serial_bls.log 2>&1
 NO_EXTRAS=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/session -- python $R/scripts/session_leg.py 22 5 > $O/session.log 2>&1

@@ -12,7 +12,7 @@ rm -rf $O; mkdir -p $O
 cd $R
 if [ "${SKIP_TESTS:-0}" != "1" ]; then timeout 2700 python -m pytest tests -x -q -m gpu > $O/pytest_gpu.txt 2>&1; timeout 900 python -m pytest tests -q -m variant > $O/pytest_variant.txt 2>&1; fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
-timeout 1200 python bench.py --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; cp bench_detail.json $O/bench_detail.json
+timeout 1200 python bench.py --full --steps 20 --warmup 5 > $O/bench_line.json 2> $O/bench.err; cp bench_detail.json $O/bench_detail.json
 timeout 900 python bench.py --gpus 2 --backend gloo --shared-device --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_n2_shared_line.json 2> $O/bench_n2_shared.err; cp bench_detail.json $O/bench_n2_shared_detail.json
 timeout 400 python scripts/fuzz_msm.py 300 11 > $O/fuzz_msm.txt 2>&1
 timeout 300 python scripts/ntt_timing.py 16,20,22,24 > $O/ntt_timing.txt 2>&1
@@ -20,7 +20,7 @@ timeout 300 python scripts/ntt_timing.py 16,20,22,24 > $O/ntt_timing.txt 2>&1
 COGROTH16_HOST_LIB=collaborative-circom_amd/libcogroth16_host_knobs.so timeout 900 python scripts/multi_device_emulation.py 22 1,2,4,8 > $O/multi_device_emulation.txt 2>&1
 for w in 2 4 8; do for r in 0 $((w-1)); do timeout 300 python bench.py --emulate $w:$r --steps 10 --warmup 3 --no-session --no-cpu-baseline 2>/dev/null | cut -c1-700 >> $O/planner_emulation.txt; done; done
 cd /tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-session > $O/stats.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-session > $O/stats.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -- python $R/scripts/serial_kernels.py 22 5 > $O/serial.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial_bls -- python $R/scripts/serial_kernels.py 22 3 bls12_381 > $O/serial_bls.log 2>&1
 NO_EXTRAS=1 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/session -- python $R/scripts/session_leg.py 22 5 > $O/session.log 2>&1

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/pmc_valu; mkdir -p $O
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU SQ_BUSY_CYCLES SQ_WAVES \
-    --output-format csv -d $O/raw -- python $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --one-context > $O/run.log 2>&1
+    --output-format csv -d $O/raw -- python $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --one-context > $O/run.log 2>&1
 cd $R
 python - <<PY
 import csv, glob, json, re

@@ -1,6 +1,6 @@
 import importlib, os, sys, tempfile
 import numpy as np, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 cg = importlib.import_module("collaborative-circom_amd")
 import bench
 log_m = 22

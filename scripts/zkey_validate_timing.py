@@ -1,5 +1,5 @@
 import importlib, os, sys, time, tempfile
-ROOT = "/root/repo" if os.path.isdir("/root/repo/tests") else os.environ.get("GRAFT_REPO_ROOT", ".")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 cg = importlib.import_module("collaborative-circom_amd")
 import oracle_lib as orc

@@ -7,6 +7,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -70,3 +71,16 @@ def test_cpu_twins_of_the_headline_legs_run_on_the_host():
     assert 0 < t < 5 and set(st) == {"rows_products_s", "ntt_s", "msm_g1_s", "msm_g2_tail_s", "mask_draws_s"}
     assert abs(sum(st.values()) - t) < 0.2 * t + 1e-3
     assert 0 < orc.bench_mask_draws(orc.BN254, 1 << 10) < 1
+
+
+def test_dump_outputs_writes_limbs_as_exact_float64_words(bench, tmp_path):
+    """--dump-outputs: uint64 limbs go out as float64 32-bit words, low word first, and come back bit for bit"""
+    rng = np.random.default_rng(3)
+    pts = rng.integers(0, 2**63, size=(2, 8), dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+    proof = rng.integers(0, 2**63, size=16, dtype=np.uint64) | np.uint64(1 << 63)
+    bench.dump_outputs(str(tmp_path / "out"), {"pts": pts, "proof_a": proof})
+    for name, want in (("pts", pts), ("proof_a", proof)):
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype == np.float64 and got.shape == want.shape[:-1] + (2 * want.shape[-1],)
+        words = got.astype(np.uint64)
+        np.testing.assert_array_equal(words[..., 0::2] | (words[..., 1::2] << np.uint64(32)), want)

@@ -137,3 +137,34 @@ def test_gpus_flag_refuses_a_box_with_too_few_gpus():
     env2 = dict(env, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu-baseline"], cwd=ROOT, env=env2, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0 and "WORLD_SIZE=1" in (p.stderr + p.stdout)
+
+
+def test_plain_run_times_the_headline_and_dumps_a_valid_proof(tmp_path):
+    """a plain N = 1 run (no --full): `--steps` proofs through the entry and nothing else on the line; --dump-outputs writes the last
+    timed proof, which verifies under the synthetic circuit's key and is the same in a second run (seeded inputs)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, ROOT)
+    import oracle_lib as orc
+    from product import cg
+    log_m, proofs = 14, {}
+    for run in (0, 1):
+        d = tmp_path / f"out{run}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--log-m", str(log_m), "--dump-outputs", str(d)]
+        env = dict(os.environ, BENCH_DETAIL=str(tmp_path / "detail.json"))
+        p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        j = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+        assert j["steps"] == 3 and j["product_entry"]["proofs"] == 3 and j["ms_per_step"] == j["product_entry"]["ms_per_proof"] > 0
+        assert j["value_basis"].startswith("product entry")
+        for key in ("step_resident", "roofline", "cpu_baseline", "sizes", "poseidon_fixture", "second_curve"):
+            assert key not in j, key
+        parts = [np.load(d / f"proof_{k}.npy") for k in "abc"]
+        assert all(a.dtype == np.float64 for a in parts)
+        words = np.concatenate(parts).astype(np.uint64)
+        proofs[run] = words[0::2] | (words[1::2] << np.uint64(32))
+    np.testing.assert_array_equal(proofs[0], proofs[1])
+    zp, wp = str(tmp_path / "s.zkey"), str(tmp_path / "s.wtns")
+    cg.host_synth_circuit(cg.BN254, log_m, 0xC0C1C0DE, zp, wp)             # bench.py's entry circuit (same seed)
+    z = orc.ZKey(orc.BN254, zp); w = orc.read_wtns(orc.BN254, wp)
+    v1, v2 = z.points("vk_g1"), z.points("vk_g2")
+    vk = {"alpha1": v1[0], "beta2": v2[0], "gamma2": v2[1], "delta2": v2[2], "ic": z.points("ic")}
+    assert orc.verify(orc.BN254, vk, w[1:1 + z.n_public], proofs[0])
