@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "cg_host_alloc", "cg_host_free", "cg_host_is_pinned", "cg_dev_download_begin", "cg_dev_upload_begin", "cg_stream_mark", "cg_dev_download_begin_after", "cg_copy_wait", "cg_copy_fence",
     "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
     "cg_spmv_csr_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
+    "cg_plonk_additions_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
     "cg_bases_synth_multiples", "cg_bases_download", "cg_bases_from_scalars",
@@ -660,6 +661,13 @@ def host_synth_circuit(curve, log_m, seed, zkey_path, wtns_path, device=0):
     _hchk(load_host().cgh_synth_circuit(int(device), curve, int(log_m), C.c_uint64(seed), zkey_path.encode(), wtns_path.encode()))
 
 
+def host_synth_plonk_circuit(curve, log_n, seed, zkey_path, wtns_path, n_public=1, n_additions=0, device=0):
+    """synthetic satisfiable Plonk circuit of domain 2^log_n (toxic waste from `seed`, p_tau by fixed-base batch multiplication and the
+    polynomials' evaluations by the library's NTT on the GPU), written as a snarkjs-format Plonk .zkey + .wtns (bench / test tooling)"""
+    _hchk(load_host().cgh_synth_plonk_circuit(int(device), curve, int(log_n), C.c_uint64(seed), C.c_uint32(n_public), C.c_uint32(n_additions),
+                                              zkey_path.encode(), wtns_path.encode()))
+
+
 def host_set_zkey_validation(on):
     """the prove entry points and session_open validate every zkey point on the GPU by default (the reference's parser does);
     callers that validated the file before can switch it off"""
@@ -957,6 +965,59 @@ def plonk_prove_rep3_party(curve, zkey_path, pub, wit_a, wit_b, net_table, rand_
                                                     int(upto), _hp(commits), _hp(ev), _hp(ch)))
     dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
     return dct
+
+
+class PlonkSession:
+    """co-plonk proving session (cgh_plonk_session_*): the zkey is read once; p_tau (validated, with per-window tables), the q / sigma /
+    Lagrange polynomials, the wire maps and the additions' level schedule stay on the device; proofs (rounds 1..5) read them there"""
+
+    def __init__(self, curve, zkey_path, precompute=True, device=0, validate=True):
+        self.curve, self.h = curve, None
+        h = C.c_void_p()
+        _hchk(load_host().cgh_plonk_session_open(int(device), curve, zkey_path.encode(), -1 if precompute is True else int(precompute),
+                                                 C.c_uint32(0 if validate else 1), C.byref(h)))
+        self.h = h
+        info = (C.c_size_t * 6)()
+        _hchk(load_host().cgh_plonk_session_info(self.h, info))
+        self.info = dict(zip(("n_vars", "n_public", "domain_size", "power", "n_additions", "n_constraints"), [int(x) for x in info]))
+
+    def close(self):
+        if self.h: load_host().cgh_plonk_session_close(self.h); self.h = None
+
+    def _outputs(self):
+        nq = 6 if self.curve == BLS12_381 else 4
+        return np.zeros((9, 2 * nq), dtype=np.uint64), np.zeros((6, 4), dtype=np.uint64), np.zeros((5, 4), dtype=np.uint64), (C.c_double * 1)()
+
+    def _rows(self, name, x, n):
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(-1, 4)
+        if x.shape[0] != n:
+            raise BackendError(f"PlonkSession: {name} has {x.shape[0]} elements, the zkey wants {n}")
+        return x
+
+    def prove_plain(self, full_witness, blind):
+        """full_witness = n_vars - n_additions elements (leading one, public inputs, private witness); returns (proof dict, seconds)"""
+        i = self.info
+        w = self._rows("full_witness", full_witness, i["n_vars"] - i["n_additions"])
+        commits, ev, ch, sec = self._outputs()
+        _hchk(load_host().cgh_plonk_session_prove_plain(self.h, _hp(w), _hp(_pad_blind(blind)), _hp(commits), _hp(ev), _hp(ch), sec))
+        dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
+        return dct, sec[0]
+
+    def prove_rep3_party(self, pub, wit_a, wit_b, net_table, rand_table, blind_a=None, blind_b=None, streams_table=None):
+        """ONE REP3 party through the callback ABI (cgh_plonk_session_prove_rep3_party); blind_a/blind_b None = drawn with rand() first.
+        Returns (proof dict, seconds).  Call it from one thread per party, each on its own session."""
+        i = self.info
+        n_priv = i["n_vars"] - i["n_additions"] - i["n_public"] - 1
+        keep = [self._rows("pub", pub, i["n_public"] + 1), self._rows("wit_a", wit_a, n_priv), self._rows("wit_b", wit_b, n_priv)]
+        bl = [None if x is None else _pad_blind(x) for x in (blind_a, blind_b)]
+        commits, ev, ch, sec = self._outputs()
+        _hchk(load_host().cgh_plonk_session_prove_rep3_party(self.h, _hp(keep[0]), _hp(keep[1]), _hp(keep[2]),
+                                                             None if bl[0] is None else _hp(bl[0]), None if bl[1] is None else _hp(bl[1]),
+                                                             C.byref(net_table), C.byref(rand_table),
+                                                             C.byref(streams_table) if streams_table is not None else None,
+                                                             _hp(commits), _hp(ev), _hp(ch), sec))
+        dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
+        return dct, sec[0]
 
 
 def plonk_prove_shamir(curve, zkey_path, n, t, pub, wits, blinds, streams, upto=5, device=0):

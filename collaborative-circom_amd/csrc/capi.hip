@@ -530,6 +530,131 @@ int32_t cg_vec_inverse_dev(cg_ctx* ctx, int32_t curve, void* d_out, const void* 
         return launch_vec_inverse<Fr>(ctx->stream, (Fr*)d_out, (const Fr*)d_in, n);
     });
 }
+// ---- co-plonk (plonk_kernels.hpp): the witness additions of round 1 and the pointwise steps of round 3, every share component per launch
+extern "C++" {
+namespace {
+// k share components (1 or 2) of `nv` vectors: pointer table entry [v * 2 + j]; every entry j < k must be set
+template <class T, class P> int plonk_table(T (*dst)[2], P const* src, int nv, int k) {
+    for (int v = 0; v < nv; v++) for (int j = 0; j < 2; j++) {
+        dst[v][j] = j < k ? (T)src[2 * v + j] : nullptr;
+        if (j < k && !dst[v][j]) return fail(CG_ERR_ARG, "null share component");
+    }
+    return 0;
+}
+int plonk_check(cg_ctx* ctx, int32_t k, int32_t pc) {
+    if (!ctx) return fail(CG_ERR_ARG, "null argument");
+    if (k < 1 || k > 2) return fail(CG_ERR_ARG, "k must be 1 or 2 share components");
+    if (pc < -1 || pc >= k) return fail(CG_ERR_ARG, "public component must be -1 or below k");
+    HIPCHK(hipSetDevice(ctx->device));
+    return 0;
+}
+}  // namespace
+}  // extern "C++"
+int32_t cg_plonk_additions_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_order, size_t n, const uint32_t* d_ids, const void* d_coeffs, const void* d_pub,
+                               uint32_t n_inputs, int32_t public_component, void* d_ext_a, void* d_ext_b, size_t n_priv) {
+    if (!ctx || !d_ext_a || (n && (!d_order || !d_ids || !d_coeffs || !d_pub))) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, d_ext_b ? 2 : 1, public_component)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_additions<Fr>(ctx->stream, d_order, n, d_ids, (const Fr*)d_coeffs, (const Fr*)d_pub, n_inputs, public_component, (Fr*)d_ext_a, (Fr*)d_ext_b, n_priv);
+    });
+}
+int32_t cg_plonk_r3_blind_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, const void* d_pw, const void* h_omega, const void* h_blind, void* const* d_out) {
+    if (!d_pw || !h_omega || !h_blind || !d_out) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, -1)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkBlindArgs<Fr> g; memset(&g, 0, sizeof g);
+        g.pw = (const Fr*)d_pw; g.k = k; copy_in(g.omega, h_omega);
+        for (int j = 0; j < k; j++) for (int t = 0; t < 9; t++) copy_in(g.b[j][t], (const char*)h_blind + (size_t)(9 * j + t) * sizeof(Fr));
+        if (int rc = plonk_table(g.out, d_out, 5, k)) return rc;
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_r3_blind<Fr>(ctx->stream, g, n);
+    });
+}
+int32_t cg_plonk_r3_perm_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_pw, const void* const* d_sigma,
+                             const void* h_coeffs, const void* const* d_wires, void* const* d_out) {
+    if (!d_pw || !d_sigma || !h_coeffs || !d_wires || !d_out) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, public_component)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkPermArgs<Fr> g; memset(&g, 0, sizeof g);
+        g.pw = (const Fr*)d_pw; g.k = k; g.pc = public_component;
+        for (int w = 0; w < 3; w++) { g.sigma[w] = (const Fr*)d_sigma[w]; if (!g.sigma[w]) return fail(CG_ERR_ARG, "null argument"); }
+        for (int t = 0; t < 4; t++) copy_in(g.coef[t], (const char*)h_coeffs + (size_t)t * sizeof(Fr));
+        if (int rc = plonk_table(g.w, d_wires, 3, k)) return rc;
+        if (int rc = plonk_table(g.out, d_out, 6, k)) return rc;
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_r3_perm<Fr>(ctx->stream, g, n);
+    });
+}
+int32_t cg_plonk_r3_gate_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* const* d_q, const void* d_lagrange, size_t n_lagrange,
+                             const void* const* d_in, const void* h_z1, void* const* d_out) {
+    if (!d_q || (n_lagrange && !d_lagrange) || !d_in || !h_z1 || !d_out) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, public_component)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkGateArgs<Fr> g; memset(&g, 0, sizeof g);
+        g.k = k; g.pc = public_component; g.lag = (const Fr*)d_lagrange; g.n_lag = n_lagrange;
+        for (int t = 0; t < 5; t++) { g.q[t] = (const Fr*)d_q[t]; if (!g.q[t]) return fail(CG_ERR_ARG, "null argument"); }
+        for (int t = 0; t < 4; t++) copy_in(g.z1[t], (const char*)h_z1 + (size_t)t * sizeof(Fr));
+        if (int rc = plonk_table(g.in, d_in, 11, k)) return rc;
+        Fr* out[2][2];
+        if (int rc = plonk_table(out, d_out, 2, k)) return rc;
+        for (int j = 0; j < 2; j++) { g.e1[j] = out[0][j]; g.e1z[j] = out[1][j]; }
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_r3_gate<Fr>(ctx->stream, g, n);
+    });
+}
+int32_t cg_plonk_mul4_tail_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, const void* const* d_prod, const void* h_z, void* const* d_rz) {
+    if (!d_prod || !h_z || !d_rz) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, -1)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkMul4Args<Fr> g; memset(&g, 0, sizeof g);
+        g.k = k;
+        for (int a = 0; a < 3; a++) for (int t = 0; t < 4; t++) copy_in(g.z[a][t], (const char*)h_z + (size_t)(4 * a + t) * sizeof(Fr));
+        if (int rc = plonk_table(g.p, d_prod, 8, k)) return rc;
+        Fr* out[1][2];
+        if (int rc = plonk_table(out, d_rz, 1, k)) return rc;
+        for (int j = 0; j < 2; j++) g.rz[j] = out[0][j];
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_mul4_tail<Fr>(ctx->stream, g, n);
+    });
+}
+int32_t cg_plonk_r3_t_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_l1, const void* const* d_in,
+                          const void* h_alpha, void* const* d_out) {
+    if (!d_l1 || !d_in || !h_alpha || !d_out) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, public_component)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkTArgs<Fr> g; memset(&g, 0, sizeof g);
+        g.k = k; g.pc = public_component; g.l1 = (const Fr*)d_l1;
+        copy_in(g.alpha, h_alpha); g.alpha2 = g.alpha * g.alpha;
+        if (int rc = plonk_table(g.in, d_in, 8, k)) return rc;
+        Fr* out[2][2];
+        if (int rc = plonk_table(out, d_out, 2, k)) return rc;
+        for (int j = 0; j < 2; j++) { g.t[j] = out[0][j]; g.tz[j] = out[1][j]; }
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_r3_t<Fr>(ctx->stream, g, n);
+    });
+}
+int32_t cg_plonk_r3_divide_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, void* const* d_t, const void* const* d_tz) {
+    if (!d_t || !d_tz) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, -1)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkDivArgs<Fr> g; memset(&g, 0, sizeof g);
+        g.k = k;
+        Fr* t[1][2]; const Fr* tz[1][2];
+        if (int rc = plonk_table(t, d_t, 1, k)) return rc;
+        if (int rc = plonk_table(tz, d_tz, 1, k)) return rc;
+        for (int j = 0; j < 2; j++) { g.t[j] = t[0][j]; g.tz[j] = tz[0][j]; }
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_r3_divide<Fr>(ctx->stream, g, n);
+    });
+}
 int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeff, size_t n_rows,
                         const void* d_pub, uint32_t n_inputs, int32_t party, const void* d_wit_a, const void* d_wit_b, void* d_out_a, void* d_out_b) {
     if (!ctx || !d_row_ptr || !d_out_a || !d_wit_a) return fail(CG_ERR_ARG, "null argument");

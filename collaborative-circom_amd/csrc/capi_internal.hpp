@@ -7,6 +7,7 @@
 #include "subgroup.hpp"
 #include "host_ec64.hpp"
 #include "ntt_kernels.hpp"   // NttVecs, plan constants (no kernels are instantiated in this translation unit)
+#include "plonk_kernels.hpp" // argument records of the co-plonk kernels (likewise)
 
 #include <cmath>
 #include <chrono>
@@ -56,6 +57,14 @@ template <class Fr> int launch_vec_gather_strided(hipStream_t st, Fr* out, const
 template <class Fr> int launch_vec_lincomb(hipStream_t st, Fr* out, long long out_off, long long out_stride, size_t n, const LincombArgs<Fr>& a);
 template <class Fr> int launch_prefix_scan(hipStream_t st, int op, Fr* out, const Fr* in, size_t n, Fr* scratch);
 template <class Fr> int launch_vec_inverse(hipStream_t st, Fr* out, const Fr* in, size_t n);
+template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* order, size_t n, const uint32_t* ids, const Fr* coeffs, const Fr* pub, uint32_t n_inputs, int pc,
+                                               Fr* ext_a, Fr* ext_b, size_t n_priv);
+template <class Fr> int launch_plonk_r3_blind(hipStream_t st, const PlonkBlindArgs<Fr>& g, size_t n);
+template <class Fr> int launch_plonk_r3_perm(hipStream_t st, const PlonkPermArgs<Fr>& g, size_t n);
+template <class Fr> int launch_plonk_r3_gate(hipStream_t st, const PlonkGateArgs<Fr>& g, size_t n);
+template <class Fr> int launch_plonk_mul4_tail(hipStream_t st, const PlonkMul4Args<Fr>& g, size_t n);
+template <class Fr> int launch_plonk_r3_t(hipStream_t st, const PlonkTArgs<Fr>& g, size_t n);
+template <class Fr> int launch_plonk_r3_divide(hipStream_t st, const PlonkDivArgs<Fr>& g, size_t n);
 template <class Fr> int launch_spmv_csr(hipStream_t st, const uint32_t* row_ptr, const uint32_t* col, const Fr* coeff, size_t n_rows, const Fr* pub,
                                         uint32_t n_inputs, int party, const Fr* wit_a, const Fr* wit_b, Fr* out_a, Fr* out_b);
 template <class Fr> int launch_build_twiddles(hipStream_t st, Fr* tw, size_t m, int log_m, const Fr* lo, const Fr* hi, int log_lo);

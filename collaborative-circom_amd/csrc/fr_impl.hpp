@@ -3,6 +3,7 @@
 #include "common.hpp"
 #include "ntt_kernels.hpp"
 #include "vec_kernels.hpp"
+#include "plonk_kernels.hpp"
 #include "msm_sort_kernels.hpp"
 
 namespace cg {
@@ -63,6 +64,28 @@ template <class Fr> int launch_vec_gather_strided(hipStream_t st, Fr* out, const
     HIPCHK(hipGetLastError());
     return 0;
 }
+// co-plonk (plonk_kernels.hpp): one launch per call, every share component in it
+template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* order, size_t n, const uint32_t* ids, const Fr* coeffs, const Fr* pub, uint32_t n_inputs, int pc,
+                                               Fr* ext_a, Fr* ext_b, size_t n_priv) {
+    if (!n) return 0;
+    hipLaunchKernelGGL((k_plonk_additions<Fr>), dim3(grid_for(n)), dim3(256), 0, st, order, n, ids, coeffs, pub, n_inputs, pc, ext_a, ext_b, n_priv);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+#define CG_PLONK_LAUNCH(NAME, KERNEL, ARGS)                                                                                  \
+    template <class Fr> int NAME(hipStream_t st, const ARGS<Fr>& g, size_t n) {                                             \
+        if (!n) return 0;                                                                                                   \
+        hipLaunchKernelGGL((KERNEL<Fr>), dim3(grid_for(n)), dim3(256), 0, st, g, n);                                         \
+        HIPCHK(hipGetLastError());                                                                                          \
+        return 0;                                                                                                           \
+    }
+CG_PLONK_LAUNCH(launch_plonk_r3_blind, k_plonk_r3_blind, PlonkBlindArgs)
+CG_PLONK_LAUNCH(launch_plonk_r3_perm, k_plonk_r3_perm, PlonkPermArgs)
+CG_PLONK_LAUNCH(launch_plonk_r3_gate, k_plonk_r3_gate, PlonkGateArgs)
+CG_PLONK_LAUNCH(launch_plonk_mul4_tail, k_plonk_mul4_tail, PlonkMul4Args)
+CG_PLONK_LAUNCH(launch_plonk_r3_t, k_plonk_r3_t, PlonkTArgs)
+CG_PLONK_LAUNCH(launch_plonk_r3_divide, k_plonk_r3_divide, PlonkDivArgs)
+#undef CG_PLONK_LAUNCH
 // scratch: ceil(n / 2048) elements; op 0 = product, 1 = sum
 template <class Fr, int OP> int launch_prefix_op(hipStream_t st, Fr* out, const Fr* in, size_t n, Fr* scratch) {
     const size_t tile = (size_t)256 * SCAN_ITEMS, ntiles = (n + tile - 1) / tile;
@@ -295,6 +318,13 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     template int launch_vec_lincomb<Fr>(hipStream_t, Fr*, long long, long long, size_t, const LincombArgs<Fr>&);           \
     template int launch_prefix_scan<Fr>(hipStream_t, int, Fr*, const Fr*, size_t, Fr*);                                    \
     template int launch_vec_inverse<Fr>(hipStream_t, Fr*, const Fr*, size_t);                                              \
+    template int launch_plonk_additions<Fr>(hipStream_t, const uint32_t*, size_t, const uint32_t*, const Fr*, const Fr*, uint32_t, int, Fr*, Fr*, size_t); \
+    template int launch_plonk_r3_blind<Fr>(hipStream_t, const PlonkBlindArgs<Fr>&, size_t);                                 \
+    template int launch_plonk_r3_perm<Fr>(hipStream_t, const PlonkPermArgs<Fr>&, size_t);                                   \
+    template int launch_plonk_r3_gate<Fr>(hipStream_t, const PlonkGateArgs<Fr>&, size_t);                                   \
+    template int launch_plonk_mul4_tail<Fr>(hipStream_t, const PlonkMul4Args<Fr>&, size_t);                                 \
+    template int launch_plonk_r3_t<Fr>(hipStream_t, const PlonkTArgs<Fr>&, size_t);                                         \
+    template int launch_plonk_r3_divide<Fr>(hipStream_t, const PlonkDivArgs<Fr>&, size_t);                                  \
     template int launch_spmv_csr<Fr>(hipStream_t, const uint32_t*, const uint32_t*, const Fr*, size_t, const Fr*, uint32_t, int, const Fr*, const Fr*, Fr*, Fr*); \
     template int launch_build_twiddles<Fr>(hipStream_t, Fr*, size_t, int, const Fr*, const Fr*, int);                      \
     template int launch_ntt_dif_pass<Fr>(hipStream_t, NttVecs, NttVecs, int, size_t, int, int, int, int, const Fr*);                \

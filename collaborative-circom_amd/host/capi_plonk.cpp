@@ -2,6 +2,10 @@
 #include "plonk.hpp"
 #include "capi_common.hpp"
 
+#include <chrono>
+#include <memory>
+#include <mutex>
+
 extern "C" {
 
 // info: n_vars, n_public, domain_size, power, n_additions, n_constraints
@@ -16,12 +20,12 @@ int32_t cgh_plonk_zkey_info(int32_t curve, const char* path, size_t* info) {
 namespace {
 struct PlonkOut { uint64_t* commits; uint64_t* challenges; uint64_t* evals; uint64_t* t_polys; uint64_t* poly_z; };
 // runs rounds 1..upto on `driver` and stores what has been computed (slot layout of cgh_plonk_prove_plain)
-void plonk_run(cgh::HipDriver& driver, const cgh::PlonkZKey& z, const cg_bases* tau, const std::vector<cgh::Fr>& pub, const cgh::ShareVec& wit, const cgh::FieldShare* b, int upto, const PlonkOut& o) {
+void plonk_run(cgh::HipDriver& driver, const cgh::PlonkResident& res, const std::vector<cgh::Fr>& pub, const cgh::ShareVec& wit, const cgh::FieldShare* b, int upto, const PlonkOut& o) {
     using namespace cgh;
-    const Curve& c = z.curve; const size_t psz = c.aff(CG_G1);
+    const Curve& c = res.z.curve; const size_t psz = c.aff(CG_G1);
     auto put = [&](int slot, const Point& p) { if (!o.commits) return; Bytes a = pt_to_affine(c, p); memcpy((uint8_t*)o.commits + slot * psz, a.data(), psz); };
     auto putf = [&](uint64_t* dst, int slot, const Fr& f) { if (dst) memcpy(dst + 4 * slot, f.v, 32); };
-    CoPlonk pk(driver, z, tau, pub, b);
+    CoPlonk pk(driver, res, pub, b);
     pk.round1(wit);
     for (int k = 0; k < 3; k++) put(k, pk.commit[k]);
     if (upto >= 2) {
@@ -40,6 +44,41 @@ void plonk_run(cgh::HipDriver& driver, const cgh::PlonkZKey& z, const cg_bases* 
     if (upto >= 5) { pk.round5(); putf(o.challenges, 4, pk.v[0]); put(7, pk.commit_wxi); put(8, pk.commit_wxiw); }
     driver.verify_received_vectors();                                              // range check of the vectors received from peers (counted on the device)
 }
+// the plain driver on `res`: full_witness = n_vars - n_additions elements (leading one, public inputs, private witness)
+void plonk_prove_plain_on(cg_ctx* ctx, const cgh::PlonkResident& res, const uint64_t* full_witness, const uint64_t* blind, int upto, const PlonkOut& o) {
+    using namespace cgh;
+    const PlonkZKey& z = res.z;
+    const Fr* w = (const Fr*)full_witness;
+    std::vector<Fr> pub(w, w + z.n_public + 1);
+    HipDriver driver(ctx, z.curve, Mode::Plain, nullptr);
+    ShareVec wit = driver.upload_vec(w + z.n_public + 1, nullptr, res.n_priv);
+    FieldShare b[11]; for (int i = 0; i < 11; i++) { memcpy(b[i].c[0].v, blind + 4 * i, 32); b[i].c[1] = b[i].c[0]; }
+    try { plonk_run(driver, res, pub, wit, b, upto, o); } catch (...) { driver.free_vec(wit); throw; }
+    driver.free_vec(wit);
+}
+// ONE REP3 party on `res` with the caller's network and randomness (cgh_plonk_prove_rep3_party_ex, cgh_plonk_session_prove_rep3_party)
+void plonk_prove_rep3_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, const uint64_t* pub_in, const uint64_t* wit_a, const uint64_t* wit_b,
+                               const uint64_t* blind_a, const uint64_t* blind_b, const cgh_rep3_net* net_cb, const cgh_rep3_rand* rnd_cb,
+                               const cgh_rep3_chacha* streams_cb, int upto, const PlonkOut& o) {
+    using namespace cgh;
+    const PlonkZKey& z = res.z;
+    std::vector<Fr> pub((const Fr*)pub_in, (const Fr*)pub_in + z.n_public + 1);
+    CallbackNetwork net(*net_cb);
+    CallbackRand rnd(*rnd_cb);
+    rnd.describe_streams(streams_cb);
+    HipDriver driver(ctx, z.curve, Mode::Rep3, &net);
+    driver.rsrc = &rnd;
+    FieldShare b[11];
+    for (int t = 0; t < 11; t++) {
+        if (blind_a) { memcpy(b[t].c[0].v, blind_a + 4 * t, 32); memcpy(b[t].c[1].v, blind_b + 4 * t, 32); }
+        else b[t] = driver.rand();
+    }
+    ShareVec wit = driver.upload_vec((const Fr*)wit_a, (const Fr*)wit_b, res.n_priv);
+    try { plonk_run(driver, res, pub, wit, b, upto, o); }
+    catch (...) { driver.free_vec(wit); throw; }
+    driver.free_vec(wit);
+    rnd.settle();
+}
 }  // namespace
 // PlainHipDriver through rounds 1..upto (<= 5).  full_witness = n_vars - n_additions Montgomery elements (Groth16-style, leading one);
 // blind = 11 Fr; commits = 9 packed G1 (a, b, c, z, t1, t2, t3, wxi, wxiw; zero = not reached), challenges = beta, gamma, alpha, xi, v;
@@ -49,22 +88,15 @@ int32_t cgh_plonk_prove_plain(int32_t device, int32_t curve, const char* zkey_pa
     cg_ctx* ctx = nullptr;
     try {
         using namespace cgh;
-        PlonkZKey z = read_plonk_zkey(curve, zkey_path);
+        PlonkZKey zk = read_plonk_zkey(curve, zkey_path);
         if (cg_ctx_create(device, &ctx)) die("cg_ctx_create");
-        const Curve& c = z.curve;
+        const Curve c = zk.curve;
         if (commits) memset(commits, 0, 9 * c.aff(CG_G1)); if (challenges) memset(challenges, 0, 5 * 32); if (evals) memset(evals, 0, 6 * 32);
-        cg_bases* tau = nullptr; CG(cg_bases_register(ctx, c.id, CG_G1, z.p_tau.data(), z.domain_size + 6, c.aff(CG_G1), -1, &tau));
-        if (validate_by_default()) { try { validate_bases(ctx, tau, "p_tau"); } catch (...) { cg_bases_release(tau); throw; } }   // the zkey parser's per-point checks
-        const Fr* w = (const Fr*)full_witness;
-        std::vector<Fr> pub(w, w + z.n_public + 1);
         {
-            HipDriver driver(ctx, c, Mode::Plain, nullptr);
-            ShareVec wit = driver.upload_vec(w + z.n_public + 1, nullptr, z.n_vars - z.n_additions - z.n_public - 1);
-            FieldShare b[11]; for (int i = 0; i < 11; i++) { memcpy(b[i].c[0].v, blind + 4 * i, 32); b[i].c[1] = b[i].c[0]; }
-            plonk_run(driver, z, tau, pub, wit, b, upto, PlonkOut{commits, challenges, evals, t_polys, poly_z});
-            driver.free_vec(wit);
+            PlonkResident res(ctx, std::move(zk), 0, validate_by_default());          // transient: this call's copy of the zkey on the device
+            plonk_prove_plain_on(ctx, res, full_witness, blind, upto, PlonkOut{commits, challenges, evals, t_polys, poly_z});
         }
-        cg_bases_release(tau); cg_ctx_destroy(ctx);
+        cg_ctx_destroy(ctx);
         return 0;
     } catch (const std::exception& e) { g_host_err = e.what(); if (ctx) cg_ctx_destroy(ctx); return 1; }
 }
@@ -94,8 +126,8 @@ int32_t cgh_plonk_prove_shamir(int32_t device, int32_t curve, const char* zkey_p
         memset(out_commits, 0, (size_t)n * 9 * psz); if (out_evals) memset(out_evals, 0, (size_t)n * 6 * 32); if (out_challenges) memset(out_challenges, 0, (size_t)n * 5 * 32);
         cg_ctx* ctx0 = nullptr;
         if (cg_ctx_create(device, &ctx0)) die("cg_ctx_create");
-        cg_bases* tau = nullptr; CG(cg_bases_register(ctx0, c.id, CG_G1, z.p_tau.data(), z.domain_size + 6, psz, -1, &tau));
-        if (validate_by_default()) { try { validate_bases(ctx0, tau, "p_tau"); } catch (...) { cg_bases_release(tau); throw; } }   // the zkey parser's per-point checks
+        std::unique_ptr<PlonkResident> res;
+        try { res.reset(new PlonkResident(ctx0, std::move(z), 0, validate_by_default())); } catch (...) { cg_ctx_destroy(ctx0); throw; }
         InProcShamirHub hub(n);
         std::vector<std::string> errs(n);
         std::vector<std::thread> th;
@@ -110,7 +142,7 @@ int32_t cgh_plonk_prove_shamir(int32_t device, int32_t curve, const char* zkey_p
                     driver.shamir_init(&net, t);
                     ShareVec w = driver.upload_vec((const Fr*)wit[i], nullptr, n_priv);
                     FieldShare b[11]; for (int q = 0; q < 11; q++) { memcpy(b[q].c[0].v, blind[i] + 4 * q, 32); b[q].c[1] = b[q].c[0]; }
-                    plonk_run(driver, z, tau, pub, w, b, upto, PlonkOut{(uint64_t*)((uint8_t*)out_commits + (size_t)i * 9 * psz), out_challenges ? out_challenges + i * 20 : nullptr,
+                    plonk_run(driver, *res, pub, w, b, upto, PlonkOut{(uint64_t*)((uint8_t*)out_commits + (size_t)i * 9 * psz), out_challenges ? out_challenges + i * 20 : nullptr,
                                                                         out_evals ? out_evals + i * 24 : nullptr, nullptr, nullptr});
                     driver.free_vec(w);
                 }
@@ -118,7 +150,7 @@ int32_t cgh_plonk_prove_shamir(int32_t device, int32_t curve, const char* zkey_p
             } catch (const std::exception& e) { errs[i] = e.what(); hub.abort(); if (ctx) cg_ctx_destroy(ctx); }
         });
         for (auto& x : th) x.join();
-        cg_bases_release(tau);
+        res.reset();
         cg_ctx_destroy(ctx0);
         if (report_party_errors(errs, n)) return 1;
         return 0;
@@ -139,8 +171,8 @@ int32_t cgh_plonk_prove_rep3(int32_t device, int32_t curve, const char* zkey_pat
         memset(out_commits, 0, 3 * 9 * psz); if (out_evals) memset(out_evals, 0, 3 * 6 * 32); if (out_challenges) memset(out_challenges, 0, 3 * 5 * 32);
         cg_ctx* ctx0 = nullptr;
         if (cg_ctx_create(device, &ctx0)) die("cg_ctx_create");
-        cg_bases* tau = nullptr; CG(cg_bases_register(ctx0, c.id, CG_G1, z.p_tau.data(), z.domain_size + 6, psz, -1, &tau));
-        if (validate_by_default()) { try { validate_bases(ctx0, tau, "p_tau"); } catch (...) { cg_bases_release(tau); throw; } }   // the zkey parser's per-point checks
+        std::unique_ptr<PlonkResident> res;
+        try { res.reset(new PlonkResident(ctx0, std::move(z), 0, validate_by_default())); } catch (...) { cg_ctx_destroy(ctx0); throw; }
         InProcHub hub;
         std::string errs[3];
         std::vector<std::thread> th;
@@ -154,7 +186,7 @@ int32_t cgh_plonk_prove_rep3(int32_t device, int32_t curve, const char* zkey_pat
                     if (streams) { driver.rng1 = (const Fr*)streams[i]; driver.rng2 = (const Fr*)streams[(i + 2) % 3]; driver.rng_len = stream_len; }
                     ShareVec wit = driver.upload_vec((const Fr*)wit_a[i], (const Fr*)wit_b[i], n_priv);
                     FieldShare b[11]; for (int t = 0; t < 11; t++) { memcpy(b[t].c[0].v, blind_a[i] + 4 * t, 32); memcpy(b[t].c[1].v, blind_b[i] + 4 * t, 32); }
-                    plonk_run(driver, z, tau, pub, wit, b, upto, PlonkOut{(uint64_t*)((uint8_t*)out_commits + (size_t)i * 9 * psz), out_challenges ? out_challenges + i * 20 : nullptr,
+                    plonk_run(driver, *res, pub, wit, b, upto, PlonkOut{(uint64_t*)((uint8_t*)out_commits + (size_t)i * 9 * psz), out_challenges ? out_challenges + i * 20 : nullptr,
                                                                           out_evals ? out_evals + i * 24 : nullptr, nullptr, nullptr});
                     driver.free_vec(wit);
                 }
@@ -162,7 +194,7 @@ int32_t cgh_plonk_prove_rep3(int32_t device, int32_t curve, const char* zkey_pat
             } catch (const std::exception& e) { errs[i] = e.what(); hub.abort(); if (ctx) cg_ctx_destroy(ctx); }
         });
         for (auto& t : th) t.join();
-        cg_bases_release(tau);
+        res.reset();
         cg_ctx_destroy(ctx0);
         if (report_party_errors(errs, 3)) return 1;
         return 0;
@@ -182,41 +214,94 @@ int32_t cgh_plonk_prove_rep3_party(int32_t device, int32_t curve, const char* zk
 int32_t cgh_plonk_prove_rep3_party_ex(int32_t device, int32_t curve, const char* zkey_path, const uint64_t* pub_in, const uint64_t* wit_a, const uint64_t* wit_b,
                                       const uint64_t* blind_a, const uint64_t* blind_b, const cgh_rep3_net* net_cb, const cgh_rep3_rand* rnd_cb,
                                       const cgh_rep3_chacha* streams_cb, int32_t upto, uint64_t* out_commits, uint64_t* out_evals, uint64_t* out_challenges) {
-    cg_ctx* ctx = nullptr; cg_bases* tau = nullptr;
+    cg_ctx* ctx = nullptr;
     try {
         using namespace cgh;
         if (!zkey_path || !pub_in || !wit_a || !wit_b || !net_cb || !rnd_cb || !out_commits) throw std::runtime_error("cgh_plonk_prove_rep3_party: null argument");
         if ((blind_a == nullptr) != (blind_b == nullptr)) throw std::runtime_error("cgh_plonk_prove_rep3_party: blind_a and blind_b go together");
         if (upto < 1 || upto > 5) throw std::runtime_error("cgh_plonk_prove_rep3_party: upto must be 1..5");
         PlonkZKey z = read_plonk_zkey(curve, zkey_path);
-        const Curve c = z.curve;
-        const size_t n_priv = z.n_vars - z.n_additions - z.n_public - 1, psz = c.aff(CG_G1);
-        std::vector<Fr> pub((const Fr*)pub_in, (const Fr*)pub_in + z.n_public + 1);
+        const size_t psz = z.curve.aff(CG_G1);
         memset(out_commits, 0, 9 * psz); if (out_evals) memset(out_evals, 0, 6 * 32); if (out_challenges) memset(out_challenges, 0, 5 * 32);
         if (cg_ctx_create(device, &ctx)) die("cg_ctx_create");
-        CG(cg_bases_register(ctx, c.id, CG_G1, z.p_tau.data(), z.domain_size + 6, psz, -1, &tau));
-        if (validate_by_default()) validate_bases(ctx, tau, "p_tau");
-        CallbackNetwork net(*net_cb);
-        CallbackRand rnd(*rnd_cb);
-        rnd.describe_streams(streams_cb);
         {
-            HipDriver driver(ctx, c, Mode::Rep3, &net);
-            driver.rsrc = &rnd;
-            FieldShare b[11];
-            for (int t = 0; t < 11; t++) {
-                if (blind_a) { memcpy(b[t].c[0].v, blind_a + 4 * t, 32); memcpy(b[t].c[1].v, blind_b + 4 * t, 32); }
-                else b[t] = driver.rand();
-            }
-            ShareVec wit = driver.upload_vec((const Fr*)wit_a, (const Fr*)wit_b, n_priv);
-            try { plonk_run(driver, z, tau, pub, wit, b, upto, PlonkOut{out_commits, out_challenges, out_evals, nullptr, nullptr}); }
-            catch (...) { driver.free_vec(wit); throw; }
-            driver.free_vec(wit);
-            rnd.settle();
+            PlonkResident res(ctx, std::move(z), 0, validate_by_default());
+            plonk_prove_rep3_party_on(ctx, res, pub_in, wit_a, wit_b, blind_a, blind_b, net_cb, rnd_cb, streams_cb, upto, PlonkOut{out_commits, out_challenges, out_evals, nullptr, nullptr});
         }
-        cg_bases_release(tau);
         cg_ctx_destroy(ctx);
         return 0;
-    } catch (const std::exception& e) { g_host_err = e.what(); if (tau) cg_bases_release(tau); if (ctx) cg_ctx_destroy(ctx); return 1; }
+    } catch (const std::exception& e) { g_host_err = e.what(); if (ctx) cg_ctx_destroy(ctx); return 1; }
+}
+
+// ---- co-plonk proving sessions: the zkey is read, uploaded and p_tau registered (validated, optionally given per-window tables) ONCE
+// (co-circom.rs:546-590 does that work once per prover process); proofs then read the resident copy (PlonkResident).  One proof at a time
+// per session; parties of one process open a session each.
+struct cgh_plonk_session {
+    cg_ctx* ctx = nullptr;
+    std::unique_ptr<cgh::PlonkResident> res;
+    std::mutex mu;
+    ~cgh_plonk_session() { res.reset(); if (ctx) cg_ctx_destroy(ctx); }
+};
+namespace {
+cgh_plonk_session* plonk_session(void* s, const char* who) { if (!s) throw std::runtime_error(std::string(who) + ": null session"); return (cgh_plonk_session*)s; }
+// a failed proof may leave work on the context's stream: wait for it (errors included) before the session serves the next proof
+void plonk_session_settle(cgh_plonk_session* s) { if (s && s->ctx) cg_ctx_sync(s->ctx); }
+}  // namespace
+int32_t cgh_plonk_session_open(int32_t device, int32_t curve, const char* zkey_path, int32_t precompute, uint32_t flags, void** out_session) {
+    cgh_plonk_session* s = nullptr;
+    try {
+        using namespace cgh;
+        if (!zkey_path || !out_session) throw std::runtime_error("cgh_plonk_session_open: null argument");
+        *out_session = nullptr;
+        PlonkZKey z = read_plonk_zkey(curve, zkey_path);
+        s = new cgh_plonk_session();
+        if (cg_ctx_create(device, &s->ctx)) die("cg_ctx_create");
+        s->res.reset(new PlonkResident(s->ctx, std::move(z), precompute, !(flags & CGH_SESSION_SKIP_VALIDATION)));
+        *out_session = s;
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); delete s; return 1; }
+}
+int32_t cgh_plonk_session_info(void* session, size_t* info) {
+    try {
+        const cgh_plonk_session* s = plonk_session(session, "cgh_plonk_session_info");
+        if (!info) throw std::runtime_error("cgh_plonk_session_info: null argument");
+        const cgh::PlonkZKey& z = s->res->z;
+        info[0] = z.n_vars; info[1] = z.n_public; info[2] = z.domain_size; info[3] = z.power; info[4] = z.n_additions; info[5] = z.n_constraints;
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
+int32_t cgh_plonk_session_close(void* session) {
+    delete (cgh_plonk_session*)session;
+    return 0;
+}
+int32_t cgh_plonk_session_prove_plain(void* session, const uint64_t* full_witness, const uint64_t* blind, uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds) {
+    cgh_plonk_session* s = nullptr;
+    try {
+        s = plonk_session(session, "cgh_plonk_session_prove_plain");
+        if (!full_witness || !blind || !commits) throw std::runtime_error("cgh_plonk_session_prove_plain: null argument");
+        std::lock_guard<std::mutex> lock(s->mu);
+        const auto t0 = std::chrono::steady_clock::now();
+        memset(commits, 0, 9 * s->res->z.curve.aff(CG_G1)); if (evals) memset(evals, 0, 6 * 32); if (challenges) memset(challenges, 0, 5 * 32);
+        plonk_prove_plain_on(s->ctx, *s->res, full_witness, blind, 5, PlonkOut{commits, challenges, evals, nullptr, nullptr});
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
+}
+int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in, const uint64_t* wit_a, const uint64_t* wit_b, const uint64_t* blind_a, const uint64_t* blind_b,
+                                           const cgh_rep3_net* net, const cgh_rep3_rand* rnd, const cgh_rep3_chacha* streams, uint64_t* commits, uint64_t* evals,
+                                           uint64_t* challenges, double* seconds) {
+    cgh_plonk_session* s = nullptr;
+    try {
+        s = plonk_session(session, "cgh_plonk_session_prove_rep3_party");
+        if (!pub_in || !wit_a || !wit_b || !net || !rnd || !commits) throw std::runtime_error("cgh_plonk_session_prove_rep3_party: null argument");
+        if ((blind_a == nullptr) != (blind_b == nullptr)) throw std::runtime_error("cgh_plonk_session_prove_rep3_party: blind_a and blind_b go together");
+        std::lock_guard<std::mutex> lock(s->mu);
+        const auto t0 = std::chrono::steady_clock::now();
+        memset(commits, 0, 9 * s->res->z.curve.aff(CG_G1)); if (evals) memset(evals, 0, 6 * 32); if (challenges) memset(challenges, 0, 5 * 32);
+        plonk_prove_rep3_party_on(s->ctx, *s->res, pub_in, wit_a, wit_b, blind_a, blind_b, net, rnd, streams, 5, PlonkOut{commits, challenges, evals, nullptr, nullptr});
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
 }
 
 }  // extern "C"

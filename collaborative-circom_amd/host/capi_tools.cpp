@@ -115,5 +115,12 @@ int32_t cgh_synth_circuit(int32_t device, int32_t curve, int32_t log_m, uint64_t
     try { cgh::synth_circuit(device, curve, log_m, seed, zkey_path, wtns_path); return 0; }
     catch (const std::exception& e) { g_host_err = e.what(); return 1; }
 }
+// synthetic satisfiable Plonk circuit of domain 2^log_n (n_public public inputs, n_additions additions) as .zkey + .wtns (tooling)
+int32_t cgh_synth_plonk_circuit(int32_t device, int32_t curve, int32_t log_n, uint64_t seed, uint32_t n_public, uint32_t n_additions, const char* zkey_path, const char* wtns_path) {
+    try {
+        if (!zkey_path || !wtns_path) throw std::runtime_error("cgh_synth_plonk_circuit: null argument");
+        cgh::synth_plonk_circuit(device, curve, log_n, seed, n_public, n_additions, zkey_path, wtns_path); return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
 
 }  // extern "C"

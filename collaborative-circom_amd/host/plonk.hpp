@@ -62,6 +62,92 @@ static PlonkZKey read_plonk_zkey(int curve_id, const std::string& path) {   // z
     return z;
 }
 
+// What a Plonk proof reads from the zkey, resident on the device: p_tau registered (and validated) once, the q and sigma polynomials in
+// both forms, the Lagrange evaluations, the one-entry CSR rows that gather the wires in round 1, the omega4^i table of round 3 and the
+// additions as a dependency-level schedule.  A session builds it once (co-circom.rs:546-590 reads the zkey once per prover process);
+// the file entry points build a transient one per call.  `z` keeps the header: its big vectors are released once they are uploaded.
+struct PlonkResident {
+    PlonkZKey z;
+    cg_ctx* ctx = nullptr;                    // the context the device copies were made with (and are freed with)
+    cg_bases* tau = nullptr;
+    void* q_eval[5] = {}; void* q_coef[5] = {}; void* sigma_eval[3] = {}; void* sigma_coef[3] = {};
+    void* lagrange = nullptr;                 // n_public vectors of 4n evaluations, back to back
+    void* pw = nullptr;                       // omega4^i, i < 4n
+    uint32_t* row_ptr = nullptr; uint32_t* col[3] = {}; void* ones = nullptr;   // round 1: wire w, row i = signal map[w][i] with coefficient one
+    // additions (round1.rs:209-238): addition a writes extended-witness entry n_priv + a; level l = order[level_off[l] .. level_off[l + 1])
+    uint32_t* add_order = nullptr; uint32_t* add_ids = nullptr; void* add_coef = nullptr;
+    std::vector<size_t> level_off;
+    size_t n_priv = 0;
+
+    PlonkResident(cg_ctx* c0, PlonkZKey&& zk, int precompute, bool validate) : z(std::move(zk)), ctx(c0) {
+        try { build(precompute, validate); } catch (...) { release(); throw; }
+    }
+    ~PlonkResident() { release(); }
+    PlonkResident(const PlonkResident&) = delete; PlonkResident& operator=(const PlonkResident&) = delete;
+
+private:
+    std::vector<void*> owned;
+    void* dev(size_t bytes) { void* p = nullptr; CG(cg_dev_alloc(ctx, std::max<size_t>(bytes, 32), &p)); owned.push_back(p); return p; }
+    void* put(const void* h, size_t bytes) { void* p = dev(bytes); if (bytes) CG(cg_dev_upload(ctx, p, h, bytes)); return p; }
+    template <class V> void* put(const V& v) { return put(v.data(), v.size() * sizeof(v[0])); }
+    void release() {
+        for (void* p : owned) cg_dev_free(ctx, p);
+        owned.clear();
+        if (tau) { cg_bases_release(tau); tau = nullptr; }
+    }
+    void build(int precompute, bool validate) {
+        const Curve& c = z.curve; const size_t n = z.domain_size, N = 4 * n, nc = z.n_constraints;
+        if (z.n_vars < z.n_additions + z.n_public + 1) throw std::runtime_error("zkey: fewer variables than additions and public inputs");
+        if (z.n_public > n) throw std::runtime_error("zkey: more public inputs than rows");   // round 3 reads buffer_a[j] for every public input j
+        n_priv = z.n_vars - z.n_additions - z.n_public - 1;
+        CG(cg_bases_register(ctx, c.id, CG_G1, z.p_tau.data(), n + 6, c.aff(CG_G1), -1, &tau));
+        if (validate) validate_bases(ctx, tau, "p_tau");                              // the zkey parser's per-point checks
+        if (precompute) {                                                              // as cgh_session_open_ex: < 0 = chosen by size
+            int window = precompute > 0 ? precompute : 0;
+            if (precompute < 0) { const size_t m = n + 6; if (m <= ((size_t)1 << 8)) window = 8; else if (m <= ((size_t)1 << 9)) window = 10; else if (m <= ((size_t)1 << 13)) window = 13; }
+            CG(cg_bases_precompute(ctx, tau, window));
+        }
+        Bytes().swap(z.p_tau);
+        for (int i = 0; i < 5; i++) { q_eval[i] = put(z.q_eval[i]); q_coef[i] = put(z.q_coef[i]); std::vector<Fr>().swap(z.q_eval[i]); std::vector<Fr>().swap(z.q_coef[i]); }
+        for (int i = 0; i < 3; i++) { sigma_eval[i] = put(z.sigma_eval[i]); sigma_coef[i] = put(z.sigma_coef[i]); std::vector<Fr>().swap(z.sigma_eval[i]); std::vector<Fr>().swap(z.sigma_coef[i]); }
+        lagrange = dev(z.n_public * N * 32);
+        for (size_t j = 0; j < z.n_public; j++) { CG(cg_dev_upload(ctx, (uint8_t*)lagrange + j * N * 32, z.lagrange_eval[j].data(), N * 32)); std::vector<Fr>().swap(z.lagrange_eval[j]); }
+        const Fr one = fr_from_u64(c, 1);
+        pw = dev(N * 32); CG(cg_vec_fill_dev(ctx, c.id, pw, N, one.v)); CG(cg_vec_distribute_powers_dev(ctx, c.id, pw, N, snarkjs_roots(c).roots[z.power + 2].v, one.v));
+        std::vector<uint32_t> rp(nc + 1); for (size_t i = 0; i <= nc; i++) rp[i] = (uint32_t)i;
+        row_ptr = (uint32_t*)put(rp);
+        for (int w = 0; w < 3; w++) { col[w] = (uint32_t*)put(z.map[w]); std::vector<uint32_t>().swap(z.map[w]); }
+        ones = dev(std::max<size_t>(nc, 1) * 32); CG(cg_vec_fill_dev(ctx, c.id, ones, std::max<size_t>(nc, 1), one.v));
+        schedule_additions();
+        CG(cg_ctx_sync(ctx));                                                          // other contexts (the parties' own) read these
+    }
+    // level 0 = public inputs and the private witness; an addition lies one level above the deeper of its operands.  An operand that is
+    // neither an input nor an EARLIER addition is what calculate_additions refuses (round1.rs:222-226).
+    void schedule_additions() {
+        const size_t na = z.additions.size(), base = z.n_public + 1;
+        std::vector<uint32_t> lvl(na), ids(2 * na); std::vector<Fr> coef(2 * na);
+        uint32_t top = 0;
+        for (size_t a = 0; a < na; a++) {
+            const auto& e = z.additions[a];
+            uint32_t l = 0;
+            for (uint32_t id : {e.id1, e.id2}) {
+                if (id < base) continue;
+                if (id >= z.n_vars || id - base >= n_priv + a) throw std::runtime_error("Cannot index into witness " + std::to_string(id));
+                if (id - base >= n_priv) l = std::max(l, lvl[id - base - n_priv]);
+            }
+            lvl[a] = l + 1; top = std::max(top, l + 1);
+            ids[2 * a] = e.id1; ids[2 * a + 1] = e.id2; coef[2 * a] = e.f1; coef[2 * a + 1] = e.f2;
+        }
+        level_off.assign(top + 1, 0);                                                  // counting sort by level
+        for (size_t a = 0; a < na; a++) level_off[lvl[a]]++;
+        for (uint32_t l = 1; l <= top; l++) level_off[l] += level_off[l - 1];
+        std::vector<uint32_t> order(na); std::vector<size_t> fill(level_off.begin(), level_off.end() - 1);
+        for (size_t a = 0; a < na; a++) order[fill[lvl[a] - 1]++] = (uint32_t)a;
+        add_order = (uint32_t*)put(order); add_ids = (uint32_t*)put(ids); add_coef = put(coef);
+        std::vector<PlonkZKey::Addition>().swap(z.additions);
+    }
+};
+
 // Keccak-256 (pad 0x01) and the reference's transcript conventions (co-plonk/src/types.rs:122-176): big-endian canonical field
 // bytes, 2 * byte_len zero bytes for the point at infinity, challenge = digest as a big-endian integer mod r
 class Keccak256 {
@@ -120,7 +206,7 @@ public:
 // evaluations) are functions of the witness and of the opened blinding values only.
 class CoPlonk {
 public:
-    HipDriver& d; const PlonkZKey& z; const cg_bases* tau;
+    HipDriver& d; const PlonkResident& r; const PlonkZKey& z; const cg_bases* tau;
     const Curve c; cg_ctx* ctx; const size_t n, N; const int k;
     Fr zero, one, omega, omega4, w2r;
     FieldShare b[11];
@@ -130,8 +216,8 @@ public:
     Fr beta, gamma, alpha, xi, v[5], ev_a, ev_b, ev_c, ev_s1, ev_s2, ev_zw;
     std::vector<ShareVec> tmp_vecs; std::vector<void*> tmp_ptrs;
 
-    CoPlonk(HipDriver& drv, const PlonkZKey& zk, const cg_bases* p_tau, const std::vector<Fr>& public_inputs, const FieldShare* blind)
-        : d(drv), z(zk), tau(p_tau), c(drv.curve), ctx(drv.ctx), n(zk.domain_size), N(4 * zk.domain_size), k(drv.k()), pub(public_inputs) {
+    CoPlonk(HipDriver& drv, const PlonkResident& res, const std::vector<Fr>& public_inputs, const FieldShare* blind)
+        : d(drv), r(res), z(res.z), tau(res.tau), c(drv.curve), ctx(drv.ctx), n(res.z.domain_size), N(4 * res.z.domain_size), k(drv.k()), pub(public_inputs) {
         if (pub.size() != z.n_public + 1) throw std::runtime_error("public input length does not match the zkey");
         zero = fr_from_u64(c, 0); one = fr_from_u64(c, 1);
         pub[0] = zero;
@@ -238,35 +324,26 @@ public:
 
     // ---- round 1 (round1.rs:118-312) ---------------------------------------------------------------------------------------------
     FieldShare trivial(const Fr& v) const { FieldShare f; f.c[0] = f.c[1] = zero; const int pc = d.public_component(); if (pc >= 0) f.c[pc] = v; return f; }
-    ShareVec extend_witness(const ShareVec& wit) {                                       // calculate_additions (:208-238)
-        const size_t n_priv = z.n_vars - z.n_additions - z.n_public - 1;
-        std::vector<Fr> ext[2];
-        for (int j = 0; j < k; j++) { ext[j].resize(n_priv + z.n_additions); if (n_priv) CG(cg_dev_download(ctx, ext[j].data(), wit.c[j], n_priv * 32)); }
-        size_t have = n_priv;
-        auto getw = [&](size_t idx) -> FieldShare {
-            if (idx <= z.n_public) return trivial(pub[idx]);
-            if (idx >= z.n_vars || idx - z.n_public - 1 >= have) throw std::runtime_error("Cannot index into witness " + std::to_string(idx));
-            FieldShare f; f.c[0] = f.c[1] = zero; for (int j = 0; j < k; j++) f.c[j] = ext[j][idx - z.n_public - 1];
-            return f;
-        };
-        for (const auto& a : z.additions) { FieldShare w1 = getw(a.id1), w2 = getw(a.id2); for (int j = 0; j < k; j++) ext[j][have] = A(M(a.f1, w1.c[j]), M(a.f2, w2.c[j])); have++; }
-        return d.upload_vec(ext[0].data(), k == 2 ? ext[1].data() : nullptr, ext[0].size());
+    // calculate_additions (:208-238) on the device: the private witness, then one launch per dependency level of the additions (every
+    // share component in it; public operands in the public component only, as trivial() makes them)
+    ShareVec extend_witness(const ShareVec& wit, const void* d_pub) {
+        ShareVec ext = d.alloc_vec(r.n_priv + z.n_additions);
+        if (r.n_priv) copy(ext, wit, r.n_priv);
+        for (size_t l = 0; l + 1 < r.level_off.size(); l++)
+            CG(cg_plonk_additions_dev(ctx, c.id, r.add_order + r.level_off[l], r.level_off[l + 1] - r.level_off[l], r.add_ids, r.add_coef, d_pub, (uint32_t)(z.n_public + 1),
+                                      d.public_component(), ext.c[0], k == 2 ? ext.c[1] : nullptr, r.n_priv));
+        return ext;
     }
     void round1(const ShareVec& private_witness) {
         const size_t nc = z.n_constraints;
-        if (private_witness.n != z.n_vars - z.n_additions - z.n_public - 1) throw std::runtime_error("witness length does not match the zkey");
-        ShareVec ext = z.n_additions ? keep(extend_witness(private_witness)) : private_witness;
+        if (private_witness.n != r.n_priv) throw std::runtime_error("witness length does not match the zkey");
         void* d_pub = upload(pub);
-        std::vector<uint32_t> row_ptr(nc + 1); for (size_t i = 0; i <= nc; i++) row_ptr[i] = (uint32_t)i;
-        uint32_t* d_rp = (uint32_t*)Tp((nc + 8) / 8 + 1); CG(cg_dev_upload(ctx, d_rp, row_ptr.data(), (nc + 1) * 4));
-        void* d_one = Tp(std::max<size_t>(nc, 1)); CG(cg_vec_fill_dev(ctx, c.id, d_one, std::max<size_t>(nc, 1), one.v));
-        uint32_t* d_col = (uint32_t*)Tp((nc + 8) / 8 + 1);
+        ShareVec ext = z.n_additions ? keep(extend_witness(private_witness, d_pub)) : private_witness;
         for (int w = 0; w < 3; w++) {
-            if (nc) CG(cg_dev_upload(ctx, d_col, z.map[w].data(), nc * 4));
             poly[w] = d.alloc_vec(n + 2);
             // the wire buffers are gathers: one-entry CSR rows with coefficient one reuse the constraint-evaluation kernel (get_witness' public /
             // private split with the REP3 party asymmetry, lib.rs:113-137)
-            CG(cg_spmv_csr_dev(ctx, c.id, d_rp, d_col, d_one, nc, d_pub, (uint32_t)(z.n_public + 1), d.party(), ext.c[0], ext.c[1], poly[w].c[0], poly[w].c[1]));
+            CG(cg_spmv_csr_dev(ctx, c.id, r.row_ptr, r.col[w], r.ones, nc, d_pub, (uint32_t)(z.n_public + 1), d.party(), ext.c[0], ext.c[1], poly[w].c[0], poly[w].c[1]));
             buf[w] = d.alloc_vec(n); copy(buf[w], poly[w], n);
             ntt(poly[w], n, omega, true);                                                // :170-172
             evl[w] = d.alloc_vec(N); copy(evl[w], poly[w], n); ntt(evl[w], N, omega4, false);   // :174-177
@@ -299,8 +376,7 @@ public:
             CG(cg_vec_affine_dev(ctx, c.id, pv, betaw, n, kk[w].v, gamma.v));
             addpub_vec(f, buf[w], pv, n);
             num = w == 0 ? f : mul(num, f, n);
-            void* d_sigma = upload(z.sigma_eval[w]);
-            CG(cg_vec_gather_strided_dev(ctx, c.id, sig, d_sigma, n, 0, 4));
+            CG(cg_vec_gather_strided_dev(ctx, c.id, sig, r.sigma_eval[w], n, 0, 4));
             CG(cg_vec_affine_dev(ctx, c.id, pv, sig, n, beta.v, gamma.v));
             ShareVec g = T(n);
             addpub_vec(g, buf[w], pv, n);
@@ -320,87 +396,67 @@ public:
         release_tmp();
     }
     // ---- round 3 (round3.rs:234-527) ---------------------------------------------------------------------------------------------
+    // The pointwise work is six fused kernels (plonk_kernels.hpp) over every share component; the products (mul_vec) are the ones of
+    // mul4vec (:17-57) and of the gate constraint, made with the same operands in the same order as before, so that a REP3 party's masks,
+    // messages and randomness positions do not move.
+    ShareVec U(size_t len) { ShareVec v; v.n = len; for (int j = 0; j < k; j++) v.c[j] = d.dalloc(len * 32); tmp_vecs.push_back(v); return v; }   // uninitialised temporary
+    static std::vector<void*> table(std::initializer_list<const ShareVec*> vs) { std::vector<void*> t; for (const ShareVec* v : vs) { t.push_back(v->c[0]); t.push_back(v->c[1]); } return t; }
     void round3() {
-        if (z.lagrange_eval.empty()) throw std::runtime_error("round 3 needs at least one public input (lagrange[0])");
+        if (z.n_public == 0) throw std::runtime_error("round 3 needs at least one public input (lagrange[0])");
         { PlonkTranscript t(c); t.add_scalar(beta); t.add_scalar(gamma); transcript_point(t, commit_z); alpha = t.get_challenge(); }   // :498-503
-        const Fr alpha2 = M(alpha, alpha), two = fr_from_u64(c, 2);
-        const Fr Z1[4] = {zero, A(neg(one), w2r), neg(two), fr_sub(c, neg(one), w2r)};     // get_z1..3 (:203-232)
-        const Fr m2w = M(neg(two), w2r);
-        const Fr Z2[4] = {zero, m2w, M(two, two), neg(m2w)};
-        const Fr tw = M(two, w2r);
-        const Fr Z3[4] = {zero, A(two, tw), neg(M(M(two, two), two)), fr_sub(c, two, tw)};
-        auto pattern = [&](const Fr* zz) { std::vector<Fr> h(N); for (size_t i = 0; i < N; i++) h[i] = zz[i & 3]; return upload(h); };
-        void* z1p = pattern(Z1); void* z2p = pattern(Z2); void* z3p = pattern(Z3);
+        const Fr two = fr_from_u64(c, 2);
+        const Fr m2w = M(neg(two), w2r), tw = M(two, w2r);
+        const Fr Z[12] = {zero, A(neg(one), w2r), neg(two), fr_sub(c, neg(one), w2r),      // get_z1..3 (:203-232)
+                          zero, m2w, M(two, two), neg(m2w),
+                          zero, A(two, tw), neg(M(M(two, two), two)), fr_sub(c, two, tw)};
         const ShareVec &a = evl[0], &bb = evl[1], &cc = evl[2], &ez = eval_z;
-        const FieldShare fzero = trivial(zero);
+        const int pc = d.public_component();
         // the blinding polynomials on the 4n-th roots of unity (:246-256, :307-322)
-        void* pw = Tp(N); CG(cg_vec_fill_dev(ctx, c.id, pw, N, one.v)); CG(cg_vec_distribute_powers_dev(ctx, c.id, pw, N, omega4.v, one.v));
-        void* pw2 = Tp(N); CG(cg_vec_mul_dev(ctx, c.id, pw2, pw, pw, N));
-        void* pww = Tp(N); CG(cg_vec_affine_dev(ctx, c.id, pww, pw, N, omega.v, nullptr));
-        void* pww2 = Tp(N); CG(cg_vec_mul_dev(ctx, c.id, pww2, pww, pww, N));
-        ShareVec ap = T(N), bp = T(N), cp = T(N), zp = T(N), zwp = T(N), t0 = T(N);
-        affine_share(ap, pw, b[0], b[1], N); affine_share(bp, pw, b[2], b[3], N); affine_share(cp, pw, b[4], b[5], N);
-        affine_share(zp, pw2, b[6], b[8], N); affine_share(t0, pw, b[7], fzero, N); add(zp, zp, t0, N);
-        affine_share(zwp, pww2, b[6], b[8], N); affine_share(t0, pww, b[7], fzero, N); add(zwp, zwp, t0, N);
-        ShareVec zw = T(N);                                                                // z(X omega): eval_z rotated by 4 (:324-327)
+        ShareVec ap = U(N), bp = U(N), cp = U(N), zp = U(N), zwp = U(N);
+        { Fr bl[18]; for (int j = 0; j < k; j++) for (int t = 0; t < 9; t++) bl[9 * j + t] = b[t].c[j];
+          const auto o = table({&ap, &bp, &cp, &zp, &zwp}); CG(cg_plonk_r3_blind_dev(ctx, c.id, k, N, r.pw, omega.v, bl, o.data())); }
+        ShareVec zw = U(N);                                                                // z(X omega): eval_z rotated by 4 (:324-327)
         copy(zw, view(ez, 4, N - 4), N - 4); copy(view(zw, N - 4, 4), ez, 4);
-        // gate constraint (:333-368)
+        // gate constraint (:333-368), the public-input polynomial included (:352-358): pi -= L_j * buffer_a[j]
         ShareVec a_b = mul(a, bb, N), a_bp = mul(a, bp, N), ap_b = mul(bb, ap, N), ap_bp = mul(ap, bp, N);
-        ShareVec a0 = T(N); add(a0, a_bp, ap_b, N); mulpub(t0, ap_bp, z1p, N); add(a0, a0, t0, N);
-        void* q[5]; for (int i = 0; i < 5; i++) q[i] = upload(z.q_eval[i]);
-        ShareVec e1 = T(N), e1z = T(N);
-        mulpub(e1, a_b, q[0], N); mulpub(t0, a, q[1], N); add(e1, e1, t0, N); mulpub(t0, bb, q[2], N); add(e1, e1, t0, N); mulpub(t0, cc, q[3], N); add(e1, e1, t0, N);
-        addpub_vec(e1, e1, q[4], N);
-        mulpub(e1z, a0, q[0], N); mulpub(t0, ap, q[1], N); add(e1z, e1z, t0, N); mulpub(t0, bp, q[2], N); add(e1z, e1z, t0, N); mulpub(t0, cp, q[3], N); add(e1z, e1z, t0, N);
-        void* l1 = nullptr;
-        for (size_t j = 0; j < z.lagrange_eval.size(); j++) {                              // public-input polynomial (:352-358): pi -= L_j * buffer_a[j]
-            void* lj = upload(z.lagrange_eval[j]); if (j == 0) l1 = lj;
-            const FieldShare aj = get(buf[0], j);
-            for (int cpn = 0; cpn < k; cpn++) { CG(cg_vec_affine_dev(ctx, c.id, t0.c[cpn], lj, N, neg(aj.c[cpn]).v, nullptr)); }
-            add(e1, e1, t0, N);
-        }
+        ShareVec e1 = U(N), e1z = U(N);
+        { const void* q[5] = {r.q_eval[0], r.q_eval[1], r.q_eval[2], r.q_eval[3], r.q_eval[4]};
+          const auto in = table({&buf[0], &a_b, &a_bp, &ap_b, &ap_bp, &a, &bb, &cc, &ap, &bp, &cp}); const auto o = table({&e1, &e1z});
+          CG(cg_plonk_r3_gate_dev(ctx, c.id, k, pc, N, q, r.lagrange, z.n_public, in.data(), Z, o.data())); }
         // permutation constraints (:370-418)
-        auto mul4 = [&](const ShareVec& Av, const ShareVec& Bv, const ShareVec& Cv, const ShareVec& Dv, const ShareVec& Dp, ShareVec& r, ShareVec& rz) {   // mul4vec + mul4vec_post (:17-72)
+        auto mul4 = [&](const ShareVec& Av, const ShareVec& Bv, const ShareVec& Cv, const ShareVec& Dv, const ShareVec& Dp, ShareVec& rr, ShareVec& rz) {   // mul4vec + mul4vec_post (:17-72)
             ShareVec AB = mul(Av, Bv, N);
             ShareVec S1 = mul(Av, bp, N); add(S1, S1, mul(ap, Bv, N), N);                  // A B' + A' B
             ShareVec CD = mul(Cv, Dv, N);
             ShareVec S2 = mul(Cv, Dp, N); add(S2, S2, mul(cp, Dv, N), N);                  // C D' + C' D
             ShareVec CpDp = mul(cp, Dp, N);
-            r = mul(AB, CD, N);
-            rz = mul(S1, CD, N); add(rz, rz, mul(AB, S2, N), N);
-            ShareVec r1 = mul(ap_bp, CD, N); add(r1, r1, mul(S1, S2, N), N); add(r1, r1, mul(AB, CpDp, N), N);
-            mulpub(t0, r1, z1p, N); add(rz, rz, t0, N);
-            ShareVec r2 = mul(S1, CpDp, N); add(r2, r2, mul(ap_bp, S2, N), N);
-            mulpub(t0, r2, z2p, N); add(rz, rz, t0, N);
-            ShareVec r3 = mul(ap_bp, CpDp, N);
-            mulpub(t0, r3, z3p, N); add(rz, rz, t0, N);
+            rr = mul(AB, CD, N);
+            const ShareVec p0 = mul(S1, CD, N), p1 = mul(AB, S2, N);
+            const ShareVec p2 = mul(ap_bp, CD, N), p3 = mul(S1, S2, N), p4 = mul(AB, CpDp, N);
+            const ShareVec p5 = mul(S1, CpDp, N), p6 = mul(ap_bp, S2, N);
+            const ShareVec p7 = mul(ap_bp, CpDp, N);
+            rz = U(N);
+            const auto pr = table({&p0, &p1, &p2, &p3, &p4, &p5, &p6, &p7}); const auto o = table({&rz});
+            CG(cg_plonk_mul4_tail_dev(ctx, c.id, k, N, pr.data(), Z, o.data()));
         };
         ShareVec e2, e2z, e3, e3z;
         {
-            void* pvv = Tp(N);
-            ShareVec fa = T(N), fb = T(N), fc = T(N);
-            CG(cg_vec_affine_dev(ctx, c.id, pvv, pw, N, beta.v, gamma.v)); addpub_vec(fa, a, pvv, N);
-            CG(cg_vec_affine_dev(ctx, c.id, pvv, pw, N, M(beta, z.k1).v, gamma.v)); addpub_vec(fb, bb, pvv, N);
-            CG(cg_vec_affine_dev(ctx, c.id, pvv, pw, N, M(beta, z.k2).v, gamma.v)); addpub_vec(fc, cc, pvv, N);
+            ShareVec fa = U(N), fb = U(N), fc = U(N), ga = U(N), gb = U(N), gc = U(N);
+            const Fr co[4] = {beta, M(beta, z.k1), M(beta, z.k2), gamma};
+            const void* sg[3] = {r.sigma_eval[0], r.sigma_eval[1], r.sigma_eval[2]};
+            const auto w = table({&a, &bb, &cc}); const auto o = table({&fa, &fb, &fc, &ga, &gb, &gc});
+            CG(cg_plonk_r3_perm_dev(ctx, c.id, k, pc, N, r.pw, sg, co, w.data(), o.data()));
             mul4(fa, fb, fc, ez, zp, e2, e2z);
-            ShareVec ga = T(N), gb = T(N), gc = T(N);
-            void* sg[3]; for (int i = 0; i < 3; i++) sg[i] = upload(z.sigma_eval[i]);
-            CG(cg_vec_affine_dev(ctx, c.id, pvv, sg[0], N, beta.v, gamma.v)); addpub_vec(ga, a, pvv, N);
-            CG(cg_vec_affine_dev(ctx, c.id, pvv, sg[1], N, beta.v, gamma.v)); addpub_vec(gb, bb, pvv, N);
-            CG(cg_vec_affine_dev(ctx, c.id, pvv, sg[2], N, beta.v, gamma.v)); addpub_vec(gc, cc, pvv, N);
             mul4(ga, gb, gc, zw, zwp, e3, e3z);
         }
         // t = e1 + alpha (e2 - e3) + alpha^2 L1 (z - 1), tz likewise from the blinding parts (:420-441)
-        ShareVec Tv = T(N), TZ = T(N);
-        sub(t0, e2, e3, N); scale(t0, t0, alpha, N); add(Tv, e1, t0, N);
-        addpub_scalar(t0, ez, neg(one), N); mulpub(t0, t0, l1, N); scale(t0, t0, alpha2, N); add(Tv, Tv, t0, N);
-        sub(t0, e2z, e3z, N); scale(t0, t0, alpha, N); add(TZ, e1z, t0, N);
-        mulpub(t0, zp, l1, N); scale(t0, t0, alpha2, N); add(TZ, TZ, t0, N);
+        ShareVec Tv = U(N), TZ = U(N);
+        { const auto in = table({&e1, &e1z, &e2, &e3, &e2z, &e3z, &ez, &zp}); const auto o = table({&Tv, &TZ});
+          CG(cg_plonk_r3_t_dev(ctx, c.id, k, pc, N, r.lagrange, in.data(), alpha.v, o.data())); }
         ntt(Tv, N, omega4, true);                                                          // :442
-        scale(view(Tv, 0, n), view(Tv, 0, n), neg(one), n);                                // neg_vec_in_place_limit (:443)
-        for (int blk = 1; blk < 4; blk++) sub(view(Tv, blk * n, n), view(Tv, (blk - 1) * n, n), view(Tv, blk * n, n), n);   // division by X^n - 1 (:445-450)
         ntt(TZ, N, omega4, true);
-        add(Tv, Tv, TZ, N);                                                                // :453
+        { void* t[2] = {Tv.c[0], Tv.c[1]}; const void* tz[2] = {TZ.c[0], TZ.c[1]};          // neg_vec_in_place_limit, division by X^n - 1, + tz (:443-453)
+          CG(cg_plonk_r3_divide_dev(ctx, c.id, k, n, t, tz)); }
         const size_t len[3] = {n + 1, n + 1, n + 6};                                        // split (:455-470)
         for (int p = 0; p < 3; p++) { tpart[p] = d.alloc_vec(len[p]); copy(tpart[p], view(Tv, (size_t)p * n, p == 2 ? n + 6 : n), p == 2 ? n + 6 : n); }
         set(tpart[0], n, b[9]);
@@ -420,7 +476,7 @@ public:
         d.verify_received_vectors();
         const std::vector<Fr> opened = d.open_many(sh);                                    // :131
         ev_a = opened[0]; ev_b = opened[1]; ev_c = opened[2]; ev_zw = opened[3];
-        ev_s1 = eval_pub_poly(upload(z.sigma_coef[0]), n, xi); ev_s2 = eval_pub_poly(upload(z.sigma_coef[1]), n, xi);
+        ev_s1 = eval_pub_poly(r.sigma_coef[0], n, xi); ev_s2 = eval_pub_poly(r.sigma_coef[1], n, xi);
         release_tmp();
     }
     void round5() {
@@ -437,8 +493,8 @@ public:
         const Fr e4 = M(M(alpha, alpha), l[0]), e24 = A(e2, e4);
         ShareVec R = T(len);                                                               // compute_r (:143-260)
         axpy(R, poly_z, e24, n + 3);
-        void* s_co[3]; for (int i = 0; i < 3; i++) s_co[i] = upload(z.sigma_coef[i]);
-        { const Fr f[5] = {M(ev_a, ev_b), ev_a, ev_b, ev_c, one}; for (int i = 0; i < 5; i++) axpy_pub(R, upload(z.q_coef[i]), f[i], n); }
+        void* const* s_co = r.sigma_coef;
+        { const Fr f[5] = {M(ev_a, ev_b), ev_a, ev_b, ev_c, one}; for (int i = 0; i < 5; i++) axpy_pub(R, r.q_coef[i], f[i], n); }
         axpy_pub(R, s_co[2], neg(M(e3, beta)), n);
         axpy(R, tpart[2], neg(M(zh, M(xin, xin))), n + 6); axpy(R, tpart[1], neg(M(zh, xin)), n + 1); axpy(R, tpart[0], neg(zh), n + 1);
         const Fr r0 = fr_sub(c, fr_sub(c, eval_pi, M(e3, A(ev_c, gamma))), e4);

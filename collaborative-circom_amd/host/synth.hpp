@@ -1,6 +1,7 @@
 // synthetic satisfiable circuit + valid Groth16 CRS written as .zkey / .wtns (bench and test tooling)
 #pragma once
 #include "groth16.hpp"
+#include "plonk.hpp"
 
 namespace cgh {
 
@@ -138,6 +139,138 @@ static void synth_circuit(int device, int curve_id, int log_m, uint64_t seed, co
     wt.begin(1, 4 + 32 + 4); wt.u32(32); wt.put(MOD_R[c.id], 32); wt.u32((uint32_t)n_vars);
     wt.begin(2, (uint64_t)n_vars * 32);
     { std::vector<Fr> can(n_vars); CG(cg_fr_to_canonical(c.id, w.data(), can.data(), n_vars)); wt.put(can.data(), n_vars * 32); }
+    wt.close();
+}
+
+// ---- synthetic satisfiable Plonk circuit (bench / test tooling) ------------------------------------------------------------------------
+// A snarkjs-format Plonk .zkey (sections 1-14 as read_plonk_zkey parses them: circom-types/src/plonk/zkey.rs:83-255, header :373-424) and
+// its .wtns, from seeded toxic waste tau, so that Plonk sessions have keys of any size: the shipped fixtures stop at domain 64.
+// Signals: 0 = one, 1..n_public public, then n_priv private (4 seeds and one output per gate), then the additions.  Rows 0..n_public-1
+// are the public-input gates (a = public j + 1, ql = 1, the row layout of round 3's pi -= L_j buffer_a[j]); the other rows up to
+// n_constraints = n - max(1, n / 16) are multiplication (qm = 1, qo = -1), addition (ql = qr = 1, qo = -1) and constant gates (qo = 1,
+// qc = -K), whose inputs a, b are drawn from every signal made before (fan-out: copy cycles longer than 2).  Addition a = f1 w[id1] +
+// f2 w[id2]: id1 continues a chain of six (a % 6 != 0), id2 is a public input (a % 3 == 0) or a seed; gates read additions too.
+// Padding rows and unused positions carry the identity permutation.  Field elements and points are stored as the readers take them
+// (the shipped keys' encoding: Montgomery limbs, packed affine points); evaluations on the 4n roots are the library's NTT at
+// omega4 = the (power + 2)-th snarkjs root, what CoPlonk::round3 assumes; vk = q(tau) G1, X_2 = tau G2.
+static void synth_plonk_circuit(int device, int curve_id, int log_n, uint64_t seed, uint32_t n_public, uint32_t n_additions,
+                                const std::string& zkey_path, const std::string& wtns_path) {
+    if (log_n < 3 || log_n > 24) throw std::runtime_error("log_n out of range (3..24)");
+    const Curve c{curve_id};
+    const size_t n = (size_t)1 << log_n, N = 4 * n, nc = n - std::max<size_t>(1, n / 16);
+    if (n_public < 1 || n_public + 2 > nc) throw std::runtime_error("n_public must be 1 .. n_constraints - 2");
+    const size_t n_seed = 4, n_gates = nc - n_public, n_priv = n_seed + n_gates;
+    const size_t n_vars = 1 + n_public + n_priv + n_additions, base = 1 + n_public;
+    SplitMix rng{seed * 0x9e3779b97f4a7c15ull + 0x51ed270b};
+    const Fr zero = fr_from_u64(c, 0), one = fr_from_u64(c, 1), minus_one = fr_sub(c, zero, one);
+    std::vector<Fr> val(n_vars, zero);                                                // signal values (additions included)
+    val[0] = one;
+    for (size_t i = 1; i < base + n_seed; i++) val[i] = random_nonzero_fr(c, rng);
+    // additions (computed first: they read public inputs, seeds and earlier additions only)
+    const size_t add0 = base + n_priv;
+    std::vector<PlonkZKey::Addition> adds(n_additions);
+    for (size_t a = 0; a < n_additions; a++) {
+        auto& e = adds[a];
+        e.id1 = (a % 6) ? (uint32_t)(add0 + a - 1) : (uint32_t)(1 + rng.next() % (n_public + n_seed));
+        e.id2 = (a % 3 == 0) ? (uint32_t)(1 + rng.next() % n_public) : (uint32_t)(base + rng.next() % n_seed);
+        e.f1 = random_nonzero_fr(c, rng); e.f2 = random_nonzero_fr(c, rng);
+        val[add0 + a] = fr_add(c, fr_mul(c, e.f1, val[e.id1]), fr_mul(c, e.f2, val[e.id2]));
+    }
+    // gates
+    std::vector<uint32_t> map[3]; for (auto& m : map) m.assign(nc, 0);
+    std::vector<Fr> q[5]; for (auto& v : q) v.assign(n, zero);                          // qm, ql, qr, qo, qc on the rows
+    for (size_t j = 0; j < n_public; j++) { map[0][j] = (uint32_t)(1 + j); q[1][j] = one; }
+    std::vector<uint32_t> pool; for (size_t i = 1; i < base + n_seed; i++) pool.push_back((uint32_t)i);
+    for (size_t a = 0; a < n_additions; a++) pool.push_back((uint32_t)(add0 + a));
+    for (size_t g = 0; g < n_gates; g++) {
+        const size_t row = n_public + g; const uint32_t out = (uint32_t)(base + n_seed + g);
+        const uint32_t sa = pool[rng.next() % pool.size()], sb = pool[rng.next() % pool.size()];
+        map[0][row] = sa; map[1][row] = sb; map[2][row] = out;
+        switch (rng.next() % 3) {
+        case 0: q[0][row] = one; q[3][row] = minus_one; val[out] = fr_mul(c, val[sa], val[sb]); break;
+        case 1: q[1][row] = one; q[2][row] = one; q[3][row] = minus_one; val[out] = fr_add(c, val[sa], val[sb]); break;
+        default: { const Fr K = random_nonzero_fr(c, rng); q[3][row] = one; q[4][row] = fr_sub(c, zero, K); val[out] = K; }
+        }
+        pool.push_back(out);
+    }
+    // k1, k2: k1^n, k2^n, (k2 / k1)^n != 1 (the three cosets are disjoint)
+    const uint64_t ne[1] = {(uint64_t)n};
+    auto coset_ok = [&](const Fr& x) { return !fr_eq(fr_pow(c, x, ne, 1), one); };
+    Fr k1 = fr_from_u64(c, 2), k2 = fr_from_u64(c, 3);
+    while (!coset_ok(k1)) k1 = fr_add(c, k1, one);
+    while (!coset_ok(k2) || !coset_ok(fr_mul(c, k2, fr_inv(c, k1)))) k2 = fr_add(c, k2, one);
+    // the permutation: positions p = w n + i labelled k_w omega^i; the positions of one signal form one cycle
+    const SnarkjsRoots rt = snarkjs_roots(c);
+    const Fr omega = rt.roots[log_n], omega4 = rt.roots[log_n + 2];
+    std::vector<Fr> wpow(n); { Fr acc = one; for (size_t i = 0; i < n; i++) { wpow[i] = acc; acc = fr_mul(c, acc, omega); } }
+    const Fr kw[3] = {one, k1, k2};
+    std::vector<uint32_t> next(3 * n); for (size_t p = 0; p < 3 * n; p++) next[p] = (uint32_t)p;
+    {
+        std::vector<int64_t> first(n_vars, -1), last(n_vars, -1);
+        for (int w = 0; w < 3; w++) for (size_t i = 0; i < nc; i++) {
+            const uint32_t s = map[w][i], p = (uint32_t)(w * n + i);
+            if (first[s] < 0) first[s] = p; else next[last[s]] = p;
+            last[s] = p;
+        }
+        for (size_t s = 0; s < n_vars; s++) if (first[s] >= 0) next[last[s]] = (uint32_t)first[s];
+    }
+    std::vector<Fr> sigma[3]; for (int w = 0; w < 3; w++) { sigma[w].resize(n); for (size_t i = 0; i < n; i++) { const uint32_t p = next[w * n + i]; sigma[w][i] = fr_mul(c, kw[p / n], wpow[p % n]); } }
+    // polynomials: coefficients = iNTT of the row values, evaluations = NTT of the zero-padded coefficients on the 4n roots
+    CtxGuard cg; if (cg_ctx_create(device, &cg.ctx)) die("cg_ctx_create");
+    cg_ctx* ctx = cg.ctx;
+    auto coef_eval = [&](const std::vector<Fr>& rows, std::vector<Fr>& co, std::vector<Fr>& ev) {
+        co = rows; void* v[1] = {co.data()};
+        CG(cg_ntt(ctx, c.id, v, 1, n, omega.v, 1, nullptr));
+        ev.assign(N, zero); std::copy(co.begin(), co.end(), ev.begin()); void* e[1] = {ev.data()};
+        CG(cg_ntt(ctx, c.id, e, 1, N, omega4.v, 0, nullptr));
+    };
+    // toxic waste: tau; p_tau = [tau^i]_1, i < n + 6; vk = q(tau) G1
+    const Fr tau = random_nonzero_fr(c, rng);
+    std::vector<Fr> tpow(n + 6); { Fr acc = one; for (auto& t : tpow) { t = acc; acc = fr_mul(c, acc, tau); } }
+    auto at_tau = [&](const std::vector<Fr>& co) { Fr acc = zero; for (size_t i = 0; i < co.size(); i++) acc = fr_add(c, acc, fr_mul(c, co[i], tpow[i])); return acc; };
+    auto g1 = [&](const Fr& k) { return pt_to_affine(c, pt_mul(c, pt_generator(c, CG_G1), k)); };
+    std::vector<Fr> q_co[5], q_ev[5], s_co[3], s_ev[3];
+    for (int i = 0; i < 5; i++) coef_eval(q[i], q_co[i], q_ev[i]);
+    for (int w = 0; w < 3; w++) coef_eval(sigma[w], s_co[w], s_ev[w]);
+    Bytes vk;
+    for (int i = 0; i < 5; i++) { Bytes b = g1(at_tau(q_co[i])); vk.insert(vk.end(), b.begin(), b.end()); }
+    for (int w = 0; w < 3; w++) { Bytes b = g1(at_tau(s_co[w])); vk.insert(vk.end(), b.begin(), b.end()); }
+    const Bytes x2 = pt_to_affine(c, pt_mul(c, pt_generator(c, CG_G2), tau));
+    Bytes ptau;
+    {
+        DevBufGuard d{ctx, nullptr};
+        CG(cg_dev_alloc(ctx, tpow.size() * 32, &d.p)); CG(cg_dev_upload(ctx, d.p, tpow.data(), tpow.size() * 32));
+        cg_bases* b = nullptr; CG(cg_bases_from_scalars(ctx, c.id, CG_G1, d.p, tpow.size(), &b));
+        ptau.resize(tpow.size() * c.aff(CG_G1));
+        const int rc = cg_bases_download(ctx, b, 0, tpow.size(), ptau.data());
+        cg_bases_release(b);
+        if (rc) die("cg_bases_download");
+    }
+    const size_t psz = c.aff(CG_G1);
+    SectionWriter zk(zkey_path, "zkey", 1, 14);
+    zk.begin(1, 4); zk.u32(2);                                                               // protocol: plonk
+    zk.begin(2, 4 + c.fq() + 4 + 32 + 20 + 64 + 8 * psz + c.aff(CG_G2));
+    zk.u32((uint32_t)c.fq()); zk.put(MOD_Q[c.id], c.fq()); zk.u32(32); zk.put(MOD_R[c.id], 32);
+    zk.u32((uint32_t)n_vars); zk.u32(n_public); zk.u32((uint32_t)n); zk.u32(n_additions); zk.u32((uint32_t)nc);
+    zk.put(k1.v, 32); zk.put(k2.v, 32); zk.put(vk.data(), vk.size()); zk.put(x2.data(), x2.size());
+    zk.begin(3, (uint64_t)n_additions * 72);
+    for (const auto& e : adds) { zk.u32(e.id1); zk.u32(e.id2); zk.put(e.f1.v, 32); zk.put(e.f2.v, 32); }
+    for (int w = 0; w < 3; w++) { zk.begin(4 + w, (uint64_t)nc * 4); zk.put(map[w].data(), nc * 4); }
+    for (int i = 0; i < 5; i++) { zk.begin(7 + i, (uint64_t)5 * n * 32); zk.put(q_co[i].data(), n * 32); zk.put(q_ev[i].data(), N * 32); }
+    zk.begin(12, (uint64_t)15 * n * 32);
+    for (int w = 0; w < 3; w++) { zk.put(s_co[w].data(), n * 32); zk.put(s_ev[w].data(), N * 32); }
+    zk.begin(13, (uint64_t)n_public * 5 * n * 32);
+    for (size_t j = 0; j < n_public; j++) {
+        std::vector<Fr> rows(n, zero), co, ev; rows[j] = one;
+        coef_eval(rows, co, ev); zk.put(co.data(), n * 32); zk.put(ev.data(), N * 32);
+    }
+    zk.begin(14, ptau.size()); zk.put(ptau.data(), ptau.size());
+    zk.close();
+    const size_t n_wit = n_vars - n_additions;                                              // .wtns: every signal but the additions
+    SectionWriter wt(wtns_path, "wtns", 2, 2);
+    wt.begin(1, 4 + 32 + 4); wt.u32(32); wt.put(MOD_R[c.id], 32); wt.u32((uint32_t)n_wit);
+    wt.begin(2, (uint64_t)n_wit * 32);
+    { std::vector<Fr> can(n_wit); CG(cg_fr_to_canonical(c.id, val.data(), can.data(), n_wit)); wt.put(can.data(), n_wit * 32); }
     wt.close();
 }
 

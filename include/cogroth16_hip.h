@@ -313,6 +313,36 @@ int32_t cg_vec_inverse_dev(cg_ctx* ctx, int32_t curve, void* d_out, const void* 
 int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeff,
                         size_t n_rows, const void* d_pub, uint32_t n_inputs, int32_t party,
                         const void* d_wit_a, const void* d_wit_b, void* d_out_a, void* d_out_b);
+/* co-plonk, every share component of a vector in one launch.  k = share components (REP3 2, plain / Shamir 1); pointer tables hold
+ * [vector * 2 + component] (entries of component 1 are ignored when k == 1); public_component = the component that holds public
+ * addends (plain / Shamir 0, REP3 party 0 -> 0, party 1 -> 1, party 2 -> -1).  Vectors are device-resident Montgomery elements.
+ *   additions: ext[n_priv + a] = f1 * w[id1] + f2 * w[id2] for a = d_order[0..n), one dependency level of the zkey's additions
+ *              (co-plonk round1.rs:209-238); d_ids = 2 u32 per addition, d_coeffs = (f1, f2) per addition; w[id] = d_pub[id] in
+ *              public_component for id < n_inputs (zero elsewhere), else ext[id - n_inputs].  d_ext_b NULL = one component.
+ *   r3_blind:  the round-3 blinding vectors ap, bp, cp, zp, zwp (round3.rs:246-256, 307-322) from pw[i] = omega4^i; h_blind = k x 9
+ *              elements (b_1..b_9 of each component); d_out = 5 x 2.
+ *   r3_perm:   fa, fb, fc (a + beta k x + gamma) and ga, gb, gc (a + beta sigma + gamma) (round3.rs:370-418); h_coeffs = beta,
+ *              beta k1, beta k2, gamma; d_sigma = 3 evaluation vectors; d_wires = 3 x 2 (a, b, c); d_out = 6 x 2.
+ *   r3_gate:   e1 (with q_c and -sum_l L_l buffer_a[l]) and e1z (round3.rs:333-368); d_q = qm, ql, qr, qo, qc; d_lagrange = n_lagrange
+ *              vectors of n elements back to back; d_in = 11 x 2: buffer_a, ab, ab', a'b, a'b', a, b, c, a', b', c'; h_z1 = Z1[0..3];
+ *              d_out = 2 x 2 (e1, e1z).
+ *   mul4_tail: rz = p0 + p1 + Z1 (p2 + p3 + p4) + Z2 (p5 + p6) + Z3 p7, Z_a[i & 3] (mul4vec_post, round3.rs:17-72); d_prod = 8 x 2;
+ *              h_z = Z1, Z2, Z3 (4 elements each); d_rz = 2.
+ *   r3_t:      t = e1 + alpha (e2 - e3) + alpha^2 L1 (z - 1), tz = e1z + alpha (e2z - e3z) + alpha^2 L1 z' (round3.rs:420-441);
+ *              d_in = 8 x 2: e1, e1z, e2, e3, e2z, e3z, z, z'; d_out = 2 x 2 (t, tz).
+ *   r3_divide: on 4n-element t, tz after their inverse NTTs: t_0 = -t_0, t_b = t_(b-1) - t_b per block of n, then t += tz
+ *              (round3.rs:443-453); n = the domain size; d_t, d_tz = 2 each. */
+int32_t cg_plonk_additions_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_order, size_t n, const uint32_t* d_ids, const void* d_coeffs, const void* d_pub,
+                               uint32_t n_inputs, int32_t public_component, void* d_ext_a, void* d_ext_b, size_t n_priv);
+int32_t cg_plonk_r3_blind_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, const void* d_pw, const void* h_omega, const void* h_blind, void* const* d_out);
+int32_t cg_plonk_r3_perm_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_pw, const void* const* d_sigma,
+                             const void* h_coeffs, const void* const* d_wires, void* const* d_out);
+int32_t cg_plonk_r3_gate_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* const* d_q, const void* d_lagrange, size_t n_lagrange,
+                             const void* const* d_in, const void* h_z1, void* const* d_out);
+int32_t cg_plonk_mul4_tail_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, const void* const* d_prod, const void* h_z, void* const* d_rz);
+int32_t cg_plonk_r3_t_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_l1, const void* const* d_in,
+                          const void* h_alpha, void* const* d_out);
+int32_t cg_plonk_r3_divide_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, void* const* d_t, const void* const* d_tz);
 /* host-buffer forms of the two elementwise products (what an unmodified `&mut Vec<F>` caller would use) */
 int32_t cg_vec_mul(cg_ctx* ctx, int32_t curve, void* h_out, const void* h_a, const void* h_b, size_t n);
 int32_t cg_vec_rep3_mul_local(cg_ctx* ctx, int32_t curve, void* h_out, const void* h_aa, const void* h_ab,

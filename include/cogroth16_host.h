@@ -270,6 +270,21 @@ int32_t cgh_plonk_prove_rep3_party_ex(int32_t device, int32_t curve, const char*
 int32_t cgh_plonk_prove_shamir(int32_t device, int32_t curve, const char* zkey_path, int32_t n, int32_t t, const uint64_t* pub_in, const uint64_t* const* wit,
                                const uint64_t* const* blind, const uint64_t* const* streams, size_t stream_len, int32_t upto,
                                uint64_t* out_commits, uint64_t* out_evals, uint64_t* out_challenges);
+/* co-plonk proving sessions: the zkey is read once; p_tau is registered (validated unless flags has CGH_SESSION_SKIP_VALIDATION, given
+ * per-window tables as precompute asks: < 0 = chosen by size, 0 = none, c = window) and the q, sigma and Lagrange polynomials, the wire maps,
+ * the omega4^i table of round 3 and the additions' level schedule stay on the device until close (co-circom.rs:546-590 reads the zkey
+ * once per prover process).  info = n_vars, n_public, domain_size, power, n_additions, n_constraints.  Proofs run rounds 1..5; outputs
+ * as for cgh_plonk_prove_plain / cgh_plonk_prove_rep3_party_ex: commits = 9 packed G1, evals = 6, challenges = 5 (both optional);
+ * seconds (optional) = wall time of the proof.  blind_a / blind_b both NULL = drawn with rand() first.  One proof at a time per session. */
+int32_t cgh_plonk_session_open(int32_t device, int32_t curve, const char* zkey_path, int32_t precompute, uint32_t flags, void** out_session);
+int32_t cgh_plonk_session_info(void* session, size_t* info);
+int32_t cgh_plonk_session_close(void* session);
+int32_t cgh_plonk_session_prove_plain(void* session, const uint64_t* full_witness, const uint64_t* blind,
+                                      uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds);
+int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in, const uint64_t* wit_a, const uint64_t* wit_b,
+                                           const uint64_t* blind_a, const uint64_t* blind_b, const cgh_rep3_net* net,
+                                           const cgh_rep3_rand* rnd, const cgh_rep3_chacha* streams,
+                                           uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds);
 /* Keccak256 transcript (co-plonk/src/types.rs:102-227): kinds[i] 0 = scalar, 1 = packed G1 point; out = the challenge */
 int32_t cgh_plonk_transcript(int32_t curve, const int32_t* kinds, const uint64_t* const* payloads, int32_t n_items, uint64_t* out_challenge);
 
@@ -277,6 +292,10 @@ int32_t cgh_plonk_transcript(int32_t curve, const int32_t* kinds, const uint64_t
 /* synthetic satisfiable circuit of 2^log_m - 2 constraints (n_public = 1, n_vars = domain size = 2^log_m) with a VALID Groth16 CRS from
  * seeded toxic waste, written as snarkjs-format .zkey + .wtns; the point tables are built on the GPU */
 int32_t cgh_synth_circuit(int32_t device, int32_t curve, int32_t log_m, uint64_t seed, const char* zkey_path, const char* wtns_path);
+/* synthetic satisfiable Plonk circuit of domain 2^log_n (3..24) from seeded toxic waste, written as a snarkjs-format Plonk .zkey (sections
+ * 1-14, p_tau = n + 6 points) + .wtns: n_public >= 1 public-input rows, multiplication / addition / constant gates with fan-out, n_additions
+ * additions in chains six deep (some over public inputs), identity permutation on the padding rows */
+int32_t cgh_synth_plonk_circuit(int32_t device, int32_t curve, int32_t log_n, uint64_t seed, uint32_t n_public, uint32_t n_additions, const char* zkey_path, const char* wtns_path);
 
 #ifdef __cplusplus
 }
