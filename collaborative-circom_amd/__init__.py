@@ -54,9 +54,9 @@ ABI_SYMBOLS = [
     "cg_msm", "cg_msm_dev", "cg_msm_dev_begin", "cg_msm_dev_begin_multi", "cg_msm_end", "cg_msm_set_window", "cg_msm_set_chunk", "cg_ctx_set_option", "cg_ctx_get_option", "cg_set_option", "cg_get_option", "cg_msm_scalars_after", "cg_msm_set_scatter_capacity",
     "cg_ntt", "cg_ntt_dev", "cg_ntt_coset_pair_dev", "cg_chacha12_fr_rand_dev", "cg_chacha12_fr_rand_dev_begin", "cg_chacha12_fr_rand_dev_finish",
     "cg_host_alloc", "cg_host_free", "cg_host_is_pinned", "cg_dev_download_begin", "cg_dev_upload_begin", "cg_stream_mark", "cg_dev_download_begin_after", "cg_copy_wait", "cg_copy_fence",
-    "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
+    "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_shamir_share_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
     "cg_spmv_csr_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
-    "cg_plonk_additions_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
+    "cg_plonk_additions_dev", "cg_plonk_r2_factors_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
     "cg_bases_synth_multiples", "cg_bases_download", "cg_bases_from_scalars",
@@ -426,6 +426,19 @@ class Context:
         offs = (C.c_int64 * k)(*[int(x) for x in src_off]); strides = (C.c_int64 * k)(*[int(x) for x in src_stride])
         _chk(load().cg_vec_lincomb_dev(self.h, curve, _dp(out), C.c_int64(out_off), C.c_int64(out_stride), C.c_size_t(n), k, ptrs, offs, strides,
                                        _hp(np.ascontiguousarray(coeffs, dtype=np.uint64))))
+
+    def shamir_share(self, curve, secrets, coeffs, coeff_off, coeff_stride, n, degree, outs, out_off=0, out_stride=1):
+        """outs[p][out_off + i*out_stride] = secrets[i] + sum_{j=1..degree} coeffs[coeff_off + i*coeff_stride + j - 1] * (p + 1)^j, all parties in one launch"""
+        ptrs = (C.c_void_p * len(outs))(*[_dp(x).value for x in outs])
+        _chk(load().cg_shamir_share_dev(self.h, curve, _dp(secrets), _dp(coeffs), C.c_int64(coeff_off), C.c_int64(coeff_stride), C.c_size_t(n), int(degree),
+                                        len(outs), ptrs, C.c_int64(out_off), C.c_int64(out_stride)))
+
+    def plonk_r2_factors(self, curve, k, public_component, n, pw, pw_stride, sigmas, sigma_stride, coeffs, wires, outs):
+        """round 2's six factors (cg_plonk_r2_factors_dev): wires = 3 x k buffers [a0, a1, b0, ..], outs = 6 x k likewise; coeffs = beta, beta k1, beta k2, gamma"""
+        tab = lambda lst: (C.c_void_p * (2 * (len(lst) // k)))(*[v for i in range(len(lst) // k) for v in ([_dp(lst[i * k + j]).value for j in range(k)] + [None] * (2 - k))])
+        sg = (C.c_void_p * 3)(*[_dp(x).value for x in sigmas])
+        _chk(load().cg_plonk_r2_factors_dev(self.h, curve, int(k), int(public_component), C.c_size_t(n), _dp(pw), C.c_size_t(pw_stride), sg, C.c_size_t(sigma_stride),
+                                            _hp(np.ascontiguousarray(coeffs, dtype=np.uint64)), tab(wires), tab(outs)))
 
     def vec_prefix_prod(self, curve, out, src, n): _chk(load().cg_vec_prefix_prod_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
     def vec_prefix_sum(self, curve, out, src, n): _chk(load().cg_vec_prefix_sum_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
@@ -967,6 +980,32 @@ def plonk_prove_rep3_party(curve, zkey_path, pub, wit_a, wit_b, net_table, rand_
     return dct
 
 
+def _shamir_extras(timing):
+    return ((C.c_double * 6)() if timing else None), (C.c_size_t * 4)()
+
+
+def _shamir_stats(rs, ps):
+    st = dict(zip(("pairs_consumed", "pairs_left", "lazy_batches", "pairs_from_device"), [int(x) for x in ps]))
+    st["round_seconds"] = None if rs is None else [float(x) for x in rs]
+    return st
+
+
+def plonk_prove_shamir_party(curve, zkey_path, threshold, pub, wit, net_table, rand_table, blind=None, preprocess=0, upto=5, device=0, timing=False):
+    """ONE Shamir party of co-plonk through the callback ABI (cgh_plonk_prove_shamir_party); blind None = drawn with rand() first.
+    Returns (proof dict, seconds, stats): stats = pairs_consumed / pairs_left / lazy_batches / pairs_from_device and, with timing=True,
+    round_seconds = [preprocessing, round 1 .. round 5].  Call it from one thread per party."""
+    nq = 6 if curve == BLS12_381 else 4
+    commits = np.zeros((9, 2 * nq), dtype=np.uint64); ch = np.zeros((5, 4), dtype=np.uint64); ev = np.zeros((6, 4), dtype=np.uint64)
+    keep = [np.ascontiguousarray(x, dtype=np.uint64) for x in (pub, wit)]
+    bl = None if blind is None else _pad_blind(blind)
+    sec = (C.c_double * 1)(); rs, ps = _shamir_extras(timing)
+    _hchk(load_host().cgh_plonk_prove_shamir_party(int(device), curve, zkey_path.encode(), int(threshold), _hp(keep[0]), _hp(keep[1]), _hp(bl),
+                                                   C.byref(net_table), C.byref(rand_table), C.c_size_t(int(preprocess)), int(upto),
+                                                   _hp(commits), _hp(ev), _hp(ch), sec, rs, ps))
+    dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
+    return dct, sec[0], _shamir_stats(rs, ps)
+
+
 class PlonkSession:
     """co-plonk proving session (cgh_plonk_session_*): the zkey is read once; p_tau (validated, with per-window tables), the q / sigma /
     Lagrange polynomials, the wire maps and the additions' level schedule stay on the device; proofs (rounds 1..5) read them there"""
@@ -1018,6 +1057,40 @@ class PlonkSession:
                                                              _hp(commits), _hp(ev), _hp(ch), sec))
         dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
         return dct, sec[0]
+
+
+    def shamir_pairs(self, threshold, with_blinding=False):
+        """double-sharing pairs ONE Shamir proof on this session consumes (cgh_plonk_session_shamir_pairs); preprocess = ceil(pairs / (t + 1))"""
+        out = C.c_size_t()
+        _hchk(load_host().cgh_plonk_session_shamir_pairs(self.h, int(threshold), int(bool(with_blinding)), C.byref(out)))
+        return int(out.value)
+
+    def _shamir_party(self, threshold, pub, wit, net_table, rand_table, seed, blind, preprocess, timing):
+        i = self.info
+        keep = [self._rows("pub", pub, i["n_public"] + 1), self._rows("wit", wit, i["n_vars"] - i["n_additions"] - i["n_public"] - 1)]
+        bl = None if blind is None else _pad_blind(blind)
+        commits, ev, ch, sec = self._outputs()
+        rs, ps = _shamir_extras(timing)
+        if seed is None:
+            _hchk(load_host().cgh_plonk_session_prove_shamir_party(self.h, int(threshold), _hp(keep[0]), _hp(keep[1]), _hp(bl), C.byref(net_table), C.byref(rand_table),
+                                                                   C.c_size_t(int(preprocess)), _hp(commits), _hp(ev), _hp(ch), sec, rs, ps))
+        else:
+            seed = bytes(seed)
+            if len(seed) != 32:
+                raise BackendError("PlonkSession: the seed is 32 bytes")
+            _hchk(load_host().cgh_plonk_session_prove_shamir_party_seeded(self.h, int(threshold), _hp(keep[0]), _hp(keep[1]), _hp(bl), C.byref(net_table), seed,
+                                                                          C.c_size_t(int(preprocess)), _hp(commits), _hp(ev), _hp(ch), sec, rs, ps))
+        dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
+        return dct, sec[0], _shamir_stats(rs, ps)
+
+    def prove_shamir_party(self, threshold, pub, wit, net_table, rand_table, blind=None, preprocess=0, timing=False):
+        """ONE Shamir party (threshold t of net_table.num_parties) through the callback ABI (cgh_plonk_session_prove_shamir_party); blind None =
+        drawn with rand() first.  Returns (proof dict, seconds, stats) like plonk_prove_shamir_party.  One thread per party, each on its own session."""
+        return self._shamir_party(threshold, pub, wit, net_table, rand_table, None, blind, preprocess, timing)
+
+    def prove_shamir_party_seeded(self, threshold, pub, wit, net_table, seed, blind=None, preprocess=0, timing=False):
+        """the same party with its private randomness as one 32-byte seed of the library's ChaCha12 stream (large draws on the GPU)"""
+        return self._shamir_party(threshold, pub, wit, net_table, None, seed, blind, preprocess, timing)
 
 
 def plonk_prove_shamir(curve, zkey_path, n, t, pub, wits, blinds, streams, upto=5, device=0):

@@ -507,6 +507,21 @@ int32_t cg_vec_lincomb_dev(cg_ctx* ctx, int32_t curve, void* d_out, int64_t out_
         return launch_vec_lincomb<Fr>(ctx->stream, (Fr*)d_out, out_off, out_stride, n, a);
     });
 }
+int32_t cg_shamir_share_dev(cg_ctx* ctx, int32_t curve, const void* d_secrets, const void* d_coeffs, int64_t coeff_off, int64_t coeff_stride, size_t len, int32_t degree,
+                            int32_t num_parties, void* const* d_outs, int64_t out_off, int64_t out_stride) {
+    if (!ctx || !d_secrets || !d_outs || (degree > 0 && !d_coeffs)) return fail(CG_ERR_ARG, "null argument");
+    if (degree < 0) return fail(CG_ERR_ARG, "cg_shamir_share_dev: negative degree");
+    if (num_parties < 1 || num_parties > SHARE_MAX_PARTIES) return fail(CG_ERR_ARG, "cg_shamir_share_dev: 1..64 parties");
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        ShareOuts<Fr> o; memset(&o, 0, sizeof o);
+        o.num_parties = num_parties;
+        for (int p = 0; p < num_parties; p++) { o.out[p] = (Fr*)d_outs[p]; if (!o.out[p]) return fail(CG_ERR_ARG, "null output vector"); }
+        StatScope ss(ctx, TAG_VEC);
+        return launch_shamir_share<Fr>(ctx->stream, (const Fr*)d_secrets, (const Fr*)d_coeffs, coeff_off, coeff_stride, len, degree, o, out_off, out_stride);
+    });
+}
 static int32_t prefix_scan_dev(cg_ctx* ctx, int32_t curve, int op, void* d_out, const void* d_in, size_t n) {
     if (!ctx || !d_out || !d_in) return fail(CG_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(ctx->device));
@@ -558,6 +573,22 @@ int32_t cg_plonk_additions_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_ord
         typedef decltype(tag) Fr;
         StatScope ss(ctx, TAG_VEC);
         return launch_plonk_additions<Fr>(ctx->stream, d_order, n, d_ids, (const Fr*)d_coeffs, (const Fr*)d_pub, n_inputs, public_component, (Fr*)d_ext_a, (Fr*)d_ext_b, n_priv);
+    });
+}
+int32_t cg_plonk_r2_factors_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_pw, size_t pw_stride, const void* const* d_sigma,
+                                size_t sigma_stride, const void* h_coeffs, const void* const* d_wires, void* const* d_out) {
+    if (!d_pw || !d_sigma || !h_coeffs || !d_wires || !d_out) return fail(CG_ERR_ARG, "null argument");
+    if (int rc = plonk_check(ctx, k, public_component)) return rc;
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkR2Args<Fr> g; memset(&g, 0, sizeof g);
+        g.pw = (const Fr*)d_pw; g.pw_stride = pw_stride; g.sigma_stride = sigma_stride; g.k = k; g.pc = public_component;
+        for (int w = 0; w < 3; w++) { g.sigma[w] = (const Fr*)d_sigma[w]; if (!g.sigma[w]) return fail(CG_ERR_ARG, "null argument"); }
+        for (int t = 0; t < 4; t++) copy_in(g.coef[t], (const char*)h_coeffs + (size_t)t * sizeof(Fr));
+        if (int rc = plonk_table(g.w, d_wires, 3, k)) return rc;
+        if (int rc = plonk_table(g.out, d_out, 6, k)) return rc;
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_r2_factors<Fr>(ctx->stream, g, n);
     });
 }
 int32_t cg_plonk_r3_blind_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, const void* d_pw, const void* h_omega, const void* h_blind, void* const* d_out) {

@@ -55,6 +55,9 @@ template <class Fr> int launch_vec_fill(hipStream_t st, Fr* v, size_t n, const F
 template <class Fr> int launch_vec_affine(hipStream_t st, Fr* out, const Fr* a, size_t n, const Fr& c, const Fr& d);
 template <class Fr> int launch_vec_gather_strided(hipStream_t st, Fr* out, const Fr* in, size_t n, size_t offset, size_t stride);
 template <class Fr> int launch_vec_lincomb(hipStream_t st, Fr* out, long long out_off, long long out_stride, size_t n, const LincombArgs<Fr>& a);
+template <class Fr> int launch_shamir_share(hipStream_t st, const Fr* secrets, const Fr* coeffs, long long coeff_off, long long coeff_stride, size_t n, int degree,
+                                            const ShareOuts<Fr>& o, long long out_off, long long out_stride);
+template <class Fr> int launch_plonk_r2_factors(hipStream_t st, const PlonkR2Args<Fr>& g, size_t n);
 template <class Fr> int launch_prefix_scan(hipStream_t st, int op, Fr* out, const Fr* in, size_t n, Fr* scratch);
 template <class Fr> int launch_vec_inverse(hipStream_t st, Fr* out, const Fr* in, size_t n);
 template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* order, size_t n, const uint32_t* ids, const Fr* coeffs, const Fr* pub, uint32_t n_inputs, int pc,

@@ -157,4 +157,9 @@ constexpr int LINCOMB_MAX = 8;
 template <class F>
 struct LincombArgs { const F* src[LINCOMB_MAX]; long long off[LINCOMB_MAX]; long long stride[LINCOMB_MAX]; F coeff[LINCOMB_MAX]; int unit[LINCOMB_MAX]; int n_terms; };
 
+// the receivers' output vectors of k_shamir_share (vec_kernels.hpp), passed by value
+constexpr int SHARE_MAX_PARTIES = 64;
+template <class F>
+struct ShareOuts { F* out[SHARE_MAX_PARTIES]; int num_parties; };
+
 }  // namespace cg

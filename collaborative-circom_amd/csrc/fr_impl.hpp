@@ -46,6 +46,13 @@ template <class Fr> int launch_vec_lincomb(hipStream_t st, Fr* out, long long ou
     HIPCHK(hipGetLastError());
     return 0;
 }
+template <class Fr> int launch_shamir_share(hipStream_t st, const Fr* secrets, const Fr* coeffs, long long coeff_off, long long coeff_stride, size_t n, int degree,
+                                            const ShareOuts<Fr>& o, long long out_off, long long out_stride) {
+    if (!n) return 0;
+    hipLaunchKernelGGL((k_shamir_share<Fr>), dim3(grid_for(n)), dim3(256), 0, st, secrets, coeffs, coeff_off, coeff_stride, n, degree, o, out_off, out_stride);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 template <class Fr> int launch_vec_gather_idx(hipStream_t st, Fr* out, const Fr* in, const uint32_t* idx, size_t n, uint32_t base) {
     if (!n) return 0;
     hipLaunchKernelGGL((k_vec_gather_idx<Fr>), dim3(grid_for(n)), dim3(256), 0, st, out, in, idx, n, base);
@@ -79,6 +86,7 @@ template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* o
         HIPCHK(hipGetLastError());                                                                                          \
         return 0;                                                                                                           \
     }
+CG_PLONK_LAUNCH(launch_plonk_r2_factors, k_plonk_r2_factors, PlonkR2Args)
 CG_PLONK_LAUNCH(launch_plonk_r3_blind, k_plonk_r3_blind, PlonkBlindArgs)
 CG_PLONK_LAUNCH(launch_plonk_r3_perm, k_plonk_r3_perm, PlonkPermArgs)
 CG_PLONK_LAUNCH(launch_plonk_r3_gate, k_plonk_r3_gate, PlonkGateArgs)
@@ -316,6 +324,8 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     template int launch_vec_affine<Fr>(hipStream_t, Fr*, const Fr*, size_t, const Fr&, const Fr&);                         \
     template int launch_vec_gather_strided<Fr>(hipStream_t, Fr*, const Fr*, size_t, size_t, size_t);                       \
     template int launch_vec_lincomb<Fr>(hipStream_t, Fr*, long long, long long, size_t, const LincombArgs<Fr>&);           \
+    template int launch_shamir_share<Fr>(hipStream_t, const Fr*, const Fr*, long long, long long, size_t, int, const ShareOuts<Fr>&, long long, long long); \
+    template int launch_plonk_r2_factors<Fr>(hipStream_t, const PlonkR2Args<Fr>&, size_t);                                  \
     template int launch_prefix_scan<Fr>(hipStream_t, int, Fr*, const Fr*, size_t, Fr*);                                    \
     template int launch_vec_inverse<Fr>(hipStream_t, Fr*, const Fr*, size_t);                                              \
     template int launch_plonk_additions<Fr>(hipStream_t, const uint32_t*, size_t, const uint32_t*, const Fr*, const Fr*, uint32_t, int, Fr*, Fr*, size_t); \

@@ -1,5 +1,5 @@
-// co-plonk elementwise kernels: the witness additions of round 1 (co-plonk/src/round1.rs:209-238) and the pointwise work of round 3
-// (round3.rs:234-470), each over every share component of a vector in one launch.  Public values enter the component that holds public
+// co-plonk elementwise kernels: the witness additions of round 1 (co-plonk/src/round1.rs:209-238), the factors of round 2's grand
+// product (round2.rs:162-216) and the pointwise work of round 3 (round3.rs:234-470), each over every share component of a vector in one launch.  Public values enter the component that holds public
 // addends (`pc`: plain / Shamir 0, REP3 party 0 -> a, party 1 -> b, party 2 -> none; rep3.rs:600-608), exactly as the generic chains
 // of CoPlonk did with add_with_public.  Field arithmetic is exact, so summing in another order gives the same bits.
 #pragma once
@@ -26,6 +26,31 @@ __global__ void __launch_bounds__(256) k_plonk_additions(const uint32_t* __restr
             const F w1 = id1 < n_inputs ? (j == pc ? ld_fp(pub + id1) : F::zero()) : ld_fp(ext + (id1 - n_inputs));
             const F w2 = id2 < n_inputs ? (j == pc ? ld_fp(pub + id2) : F::zero()) : ld_fp(ext + (id2 - n_inputs));
             st_fp(ext + n_priv + a, f1 * w1 + f2 * w2);
+        }
+    }
+}
+
+// ---- round 2 ------------------------------------------------------------------------------------------------------------------------
+// The six factors of the grand product on the domain (round2.rs:162-216): num_w = buf_w + beta k_w omega^i + gamma and
+// den_w = buf_w + beta sigma_w(omega^i) + gamma for w = a, b, c; the public addends in pc only.  omega^i = pw[i * pw_stride] (the
+// omega4^i table with a stride of 4, or a table of its own), sigma_w(omega^i) = sigma[w][i * sigma_stride] (the 4n evaluations of the
+// zkey with a stride of 4: no gathered copy).  coef = beta, beta k1, beta k2, gamma.  out: num_a, num_b, num_c, den_a, den_b, den_c.
+template <class F> struct PlonkR2Args { const F* pw; size_t pw_stride; const F* sigma[3]; size_t sigma_stride; F coef[4]; const F* w[3][2]; F* out[6][2]; int k, pc; };
+template <class F>
+__global__ void __launch_bounds__(256) k_plonk_r2_factors(PlonkR2Args<F> g, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        F pf[3], pg[3];
+        if (g.pc >= 0) {
+            const F x = ld_fp(g.pw + i * g.pw_stride);
+            _Pragma("unroll") for (int w = 0; w < 3; w++) { pf[w] = g.coef[w] * x + g.coef[3]; pg[w] = g.coef[0] * ld_fp(g.sigma[w] + i * g.sigma_stride) + g.coef[3]; }
+        }
+        _Pragma("unroll") for (int j = 0; j < 2; j++) {
+            if (j >= g.k) break;
+            _Pragma("unroll") for (int w = 0; w < 3; w++) {
+                const F v = ld_fp(g.w[w][j] + i);
+                st_fp(g.out[w][j] + i, j == g.pc ? v + pf[w] : v);
+                st_fp(g.out[3 + w][j] + i, j == g.pc ? v + pg[w] : v);
+            }
         }
     }
 }

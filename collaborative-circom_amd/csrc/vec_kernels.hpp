@@ -169,6 +169,40 @@ __global__ void __launch_bounds__(256) k_vec_lincomb(F* __restrict__ out, long l
     }
 }
 
+// ShamirCore::share (shamir_core.rs:8-31) for every receiver in ONE launch: element i's polynomial s_i + c_1 x + .. + c_d x^d, with
+// c_j = coeffs[coeff_off + i * coeff_stride + j - 1] (the draws as they come: element by element, `degree` coefficients each), is
+// evaluated by Horner at x = 1 .. num_parties and stored to out[p][out_off + i * out_stride].  Secrets and coefficients are read once
+// (up to SHARE_REG_DEGREE coefficients are held in registers; longer polynomials re-read theirs, which then come from the caches).
+// A lane reads its secret before it writes, so out[p] may be the secrets' own vector when out_off = 0 and out_stride = 1.
+constexpr int SHARE_REG_DEGREE = 4;
+template <class F>
+__global__ void __launch_bounds__(256) k_shamir_share(const F* secrets, const F* __restrict__ coeffs, long long coeff_off, long long coeff_stride, size_t n, int degree,
+                                                      ShareOuts<F> o, long long out_off, long long out_stride) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const F s = ld_fp(secrets + i);
+        const F* c = coeffs + (coeff_off + (long long)i * coeff_stride);
+        const long long at = out_off + (long long)i * out_stride;
+        F x = F::one();                                                            // the receiver's point p + 1, in Montgomery form
+        if (degree <= SHARE_REG_DEGREE) {
+            F cr[SHARE_REG_DEGREE];
+            _Pragma("unroll") for (int j = 0; j < SHARE_REG_DEGREE; j++) cr[j] = j < degree ? ld_fp(c + j) : F::zero();
+            for (int p = 0; p < o.num_parties; p++) {
+                F acc = F::zero();
+                _Pragma("unroll") for (int j = SHARE_REG_DEGREE - 1; j >= 0; j--) if (j < degree) acc = (acc + cr[j]) * x;
+                st_fp(o.out[p] + at, acc + s);
+                x = x + F::one();
+            }
+        } else {
+            for (int p = 0; p < o.num_parties; p++) {
+                F acc = F::zero();
+                for (int j = degree - 1; j >= 0; j--) acc = (acc + ld_fp(c + j)) * x;
+                st_fp(o.out[p] + at, acc + s);
+                x = x + F::one();
+            }
+        }
+    }
+}
+
 // out[j] = in[idx[j] - base]   (scalars of the non-infinity bases of a compacted table, see cg_bases::compact)
 template <class F>
 __global__ void __launch_bounds__(256) k_vec_gather_idx(F* __restrict__ out, const F* __restrict__ in, const uint32_t* __restrict__ idx, size_t n, uint32_t base) {

@@ -20,28 +20,40 @@ int32_t cgh_plonk_zkey_info(int32_t curve, const char* path, size_t* info) {
 namespace {
 struct PlonkOut { uint64_t* commits; uint64_t* challenges; uint64_t* evals; uint64_t* t_polys; uint64_t* poly_z; };
 // runs rounds 1..upto on `driver` and stores what has been computed (slot layout of cgh_plonk_prove_plain)
-void plonk_run(cgh::HipDriver& driver, const cgh::PlonkResident& res, const std::vector<cgh::Fr>& pub, const cgh::ShareVec& wit, const cgh::FieldShare* b, int upto, const PlonkOut& o) {
+// round_seconds (optional): wall time of rounds 1..5, the stream drained once after each round
+void plonk_run(cgh::HipDriver& driver, const cgh::PlonkResident& res, const std::vector<cgh::Fr>& pub, const cgh::ShareVec& wit, const cgh::FieldShare* b, int upto, const PlonkOut& o,
+               double* round_seconds = nullptr) {
     using namespace cgh;
+    auto last = std::chrono::steady_clock::now();
+    auto lap = [&](int round) {
+        if (!round_seconds) return;
+        CG(cg_ctx_sync(driver.ctx));
+        const auto now = std::chrono::steady_clock::now(); round_seconds[round - 1] = std::chrono::duration<double>(now - last).count(); last = now;
+    };
     const Curve& c = res.z.curve; const size_t psz = c.aff(CG_G1);
     auto put = [&](int slot, const Point& p) { if (!o.commits) return; Bytes a = pt_to_affine(c, p); memcpy((uint8_t*)o.commits + slot * psz, a.data(), psz); };
     auto putf = [&](uint64_t* dst, int slot, const Fr& f) { if (dst) memcpy(dst + 4 * slot, f.v, 32); };
     CoPlonk pk(driver, res, pub, b);
     pk.round1(wit);
     for (int k = 0; k < 3; k++) put(k, pk.commit[k]);
+    lap(1);
     if (upto >= 2) {
         pk.round2(); put(3, pk.commit_z); putf(o.challenges, 0, pk.beta); putf(o.challenges, 1, pk.gamma);
         if (o.poly_z) CG(cg_dev_download(driver.ctx, o.poly_z, pk.poly_z.c[0], pk.poly_z.n * 32));
+        lap(2);
     }
     if (upto >= 3) {
         pk.round3(); for (int k = 0; k < 3; k++) put(4 + k, pk.commit_t[k]); putf(o.challenges, 2, pk.alpha);
         if (o.t_polys) { size_t off = 0; for (int k = 0; k < 3; k++) { CG(cg_dev_download(driver.ctx, o.t_polys + off * 4, pk.tpart[k].c[0], pk.tpart[k].n * 32)); off += pk.tpart[k].n; } }
+        lap(3);
     }
     if (upto >= 4) {
         pk.round4(); putf(o.challenges, 3, pk.xi);
         const Fr ev[6] = {pk.ev_a, pk.ev_b, pk.ev_c, pk.ev_s1, pk.ev_s2, pk.ev_zw};
         for (int i = 0; i < 6; i++) putf(o.evals, i, ev[i]);
+        lap(4);
     }
-    if (upto >= 5) { pk.round5(); putf(o.challenges, 4, pk.v[0]); put(7, pk.commit_wxi); put(8, pk.commit_wxiw); }
+    if (upto >= 5) { pk.round5(); putf(o.challenges, 4, pk.v[0]); put(7, pk.commit_wxi); put(8, pk.commit_wxiw); lap(5); }
     driver.verify_received_vectors();                                              // range check of the vectors received from peers (counted on the device)
 }
 // the plain driver on `res`: full_witness = n_vars - n_additions elements (leading one, public inputs, private witness)
@@ -78,6 +90,54 @@ void plonk_prove_rep3_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, const
     catch (...) { driver.free_vec(wit); throw; }
     driver.free_vec(wit);
     rnd.settle();
+}
+// ---- ONE Shamir party (co-circom.rs:507-527 with the plonk prover): the caller's any-to-any network, its private randomness as a callback
+// table or as a seed of the library's own ChaCha12 stream
+// Double sharings ONE co-plonk proof consumes on a domain of n rows (N = 4n), read off CoPlonk's calls — every exchanging mul_vec of m
+// elements and every rand_vec(m) pops m pairs, a scalar rand() one; the degree-2t openings (mul_open_vec), the point openings and
+// rounds 1, 4 and 5 pop none:
+//   round 2 (round2.rs:162-229)   4 n            num b, den b, num c, den c
+//                                 2 (4 n + 2)    array_prod_mul x 2: rand_vec(n + 1), inv_many's rand_vec(n + 1), two mul_vec of n
+//                                 2 n            inv_many(den)'s rand_vec(n), z = num * den^-1
+//   round 3 (round3.rs:17-72, 333-418)  36 N     the gate constraint's 4 products and 2 x 16 of mul4vec, each of N = 4 n elements
+//   blindings drawn inside        11             b_1..b_11 with rand() (round1.rs:93-99)
+// = 158 n + 4 (+ 11).  It depends on the zkey through the domain size only: neither n_public, the additions nor the threshold enter.
+size_t plonk_shamir_pairs(const cgh::PlonkZKey& z, bool with_blinding) { return 158 * z.domain_size + 4 + (with_blinding ? 11 : 0); }
+// what the three party entries refuse before a session, a file or a device is looked at
+void shamir_party_args(const char* who, int32_t threshold, const cgh_shamir_net* net, const cgh_shamir_rand* rnd, const uint8_t* seed32, const void* pub_in, const void* wit, const void* commits) {
+    const std::string w(who);
+    if (!pub_in || !wit || !net || (!rnd && !seed32) || !commits) throw std::runtime_error(w + ": null argument");
+    if (rnd && !rnd->random_field_elements) throw std::runtime_error("cgh_shamir_rand: random_field_elements is required");
+    if (net->num_parties < 3) throw std::runtime_error(w + ": Shamir protocol requires at least 3 parties");
+    if (threshold < 0 || 2 * (int64_t)threshold + 1 > net->num_parties) throw std::runtime_error(w + ": Threshold too large for number of parties");
+}
+// round_seconds[6]: preprocessing, rounds 1..5 (round 1 includes drawing the blindings and the witness upload); pair_stats[4]: pairs
+// consumed, pairs left, lazy buffer_triples batches, pairs read from the device-resident block
+void plonk_prove_shamir_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit_in, const uint64_t* blind,
+                                 const cgh_shamir_net* net_cb, const cgh_shamir_rand* rnd_cb, const uint8_t* seed32, size_t preprocess, int upto, const PlonkOut& o,
+                                 double* round_seconds, size_t* pair_stats) {
+    using namespace cgh;
+    const PlonkZKey& z = res.z;
+    std::vector<Fr> pub((const Fr*)pub_in, (const Fr*)pub_in + z.n_public + 1);
+    CallbackShamirNet net(*net_cb);
+    HipDriver driver(ctx, z.curve, Mode::Shamir, nullptr);
+    driver.sh_rand = rnd_cb;
+    if (seed32) { driver.sh_gen = ChaCha12(seed32); driver.sh_gen_on = true; }
+    driver.shamir_init(&net, threshold);                                               // ShamirProtocol::new, shamir.rs:211-246
+    if (round_seconds) for (int i = 0; i < 6; i++) round_seconds[i] = 0;
+    const auto t0 = std::chrono::steady_clock::now();
+    driver.preprocess(preprocess);                                                     // shamir.rs:248-250; 0 = lazy batches of 1024
+    if (round_seconds) { CG(cg_ctx_sync(ctx)); round_seconds[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+    FieldShare b[11];
+    for (int q = 0; q < 11; q++) {
+        if (blind) { memcpy(b[q].c[0].v, blind + 4 * q, 32); b[q].c[1] = b[q].c[0]; }
+        else b[q] = driver.rand();                                                      // round1.rs:93-99, before anything else
+    }
+    ShareVec wit = driver.upload_vec((const Fr*)wit_in, nullptr, res.n_priv);
+    try { plonk_run(driver, res, pub, wit, b, upto, o, round_seconds ? round_seconds + 1 : nullptr); }
+    catch (...) { driver.free_vec(wit); throw; }
+    driver.free_vec(wit);
+    if (pair_stats) { pair_stats[0] = driver.pairs_consumed; pair_stats[1] = driver.sh_r_t.size(); pair_stats[2] = driver.lazy_batches; pair_stats[3] = driver.pairs_from_device; }
 }
 }  // namespace
 // PlainHipDriver through rounds 1..upto (<= 5).  full_witness = n_vars - n_additions Montgomery elements (Groth16-style, leading one);
@@ -233,6 +293,32 @@ int32_t cgh_plonk_prove_rep3_party_ex(int32_t device, int32_t curve, const char*
     } catch (const std::exception& e) { g_host_err = e.what(); if (ctx) cg_ctx_destroy(ctx); return 1; }
 }
 
+// ONE Shamir party of n (net->num_parties) with threshold t through rounds 1..upto on a transient copy of the zkey
+int32_t cgh_plonk_prove_shamir_party(int32_t device, int32_t curve, const char* zkey_path, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind,
+                                     const cgh_shamir_net* net, const cgh_shamir_rand* rnd, size_t preprocess, int32_t upto, uint64_t* out_commits, uint64_t* out_evals,
+                                     uint64_t* out_challenges, double* seconds, double* round_seconds, size_t* pair_stats) {
+    cg_ctx* ctx = nullptr;
+    try {
+        using namespace cgh;
+        if (!zkey_path || !rnd) throw std::runtime_error("cgh_plonk_prove_shamir_party: null argument");
+        shamir_party_args("cgh_plonk_prove_shamir_party", threshold, net, rnd, nullptr, pub_in, wit, out_commits);
+        if (upto < 1 || upto > 5) throw std::runtime_error("cgh_plonk_prove_shamir_party: upto must be 1..5");
+        PlonkZKey z = read_plonk_zkey(curve, zkey_path);
+        const size_t psz = z.curve.aff(CG_G1);
+        memset(out_commits, 0, 9 * psz); if (out_evals) memset(out_evals, 0, 6 * 32); if (out_challenges) memset(out_challenges, 0, 5 * 32);
+        if (cg_ctx_create(device, &ctx)) die("cg_ctx_create");
+        const auto t0 = std::chrono::steady_clock::now();
+        {
+            PlonkResident res(ctx, std::move(z), 0, validate_by_default());
+            plonk_prove_shamir_party_on(ctx, res, threshold, pub_in, wit, blind, net, rnd, nullptr, preprocess, upto, PlonkOut{out_commits, out_challenges, out_evals, nullptr, nullptr},
+                                        round_seconds, pair_stats);
+        }
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        cg_ctx_destroy(ctx);
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); if (ctx) { cg_ctx_sync(ctx); cg_ctx_destroy(ctx); } return 1; }
+}
+
 // ---- co-plonk proving sessions: the zkey is read, uploaded and p_tau registered (validated, optionally given per-window tables) ONCE
 // (co-circom.rs:546-590 does that work once per prover process); proofs then read the resident copy (PlonkResident).  One proof at a time
 // per session; parties of one process open a session each.
@@ -302,6 +388,43 @@ int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return 0;
     } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
+}
+// ONE Shamir party on a session (the twin of cgh_session_prove_shamir_party{,_seeded}); rnd or seed32, never both
+static int32_t plonk_session_shamir_party(const char* who, void* session, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind, const cgh_shamir_net* net,
+                                          const cgh_shamir_rand* rnd, const uint8_t* seed32, size_t preprocess, uint64_t* commits, uint64_t* evals, uint64_t* challenges,
+                                          double* seconds, double* round_seconds, size_t* pair_stats) {
+    cgh_plonk_session* s = nullptr;
+    try {
+        shamir_party_args(who, threshold, net, rnd, seed32, pub_in, wit, commits);
+        s = plonk_session(session, who);
+        std::lock_guard<std::mutex> lock(s->mu);
+        const auto t0 = std::chrono::steady_clock::now();
+        memset(commits, 0, 9 * s->res->z.curve.aff(CG_G1)); if (evals) memset(evals, 0, 6 * 32); if (challenges) memset(challenges, 0, 5 * 32);
+        plonk_prove_shamir_party_on(s->ctx, *s->res, threshold, pub_in, wit, blind, net, rnd, seed32, preprocess, 5, PlonkOut{commits, challenges, evals, nullptr, nullptr}, round_seconds, pair_stats);
+        if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
+}
+int32_t cgh_plonk_session_prove_shamir_party(void* session, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind, const cgh_shamir_net* net,
+                                             const cgh_shamir_rand* rnd, size_t preprocess, uint64_t* commits, uint64_t* evals, uint64_t* challenges,
+                                             double* seconds, double* round_seconds, size_t* pair_stats) {
+    if (!rnd) { g_host_err = "cgh_plonk_session_prove_shamir_party: null argument"; return 1; }
+    return plonk_session_shamir_party("cgh_plonk_session_prove_shamir_party", session, threshold, pub_in, wit, blind, net, rnd, nullptr, preprocess, commits, evals, challenges, seconds, round_seconds, pair_stats);
+}
+int32_t cgh_plonk_session_prove_shamir_party_seeded(void* session, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind, const cgh_shamir_net* net,
+                                                    const uint8_t* seed32, size_t preprocess, uint64_t* commits, uint64_t* evals, uint64_t* challenges,
+                                                    double* seconds, double* round_seconds, size_t* pair_stats) {
+    if (!seed32) { g_host_err = "cgh_plonk_session_prove_shamir_party_seeded: null argument"; return 1; }
+    return plonk_session_shamir_party("cgh_plonk_session_prove_shamir_party_seeded", session, threshold, pub_in, wit, blind, net, nullptr, seed32, preprocess, commits, evals, challenges, seconds, round_seconds, pair_stats);
+}
+int32_t cgh_plonk_session_shamir_pairs(void* session, int32_t threshold, int32_t with_blinding, size_t* out_pairs) {
+    try {
+        if (!out_pairs) throw std::runtime_error("cgh_plonk_session_shamir_pairs: null argument");
+        if (threshold < 0) throw std::runtime_error("cgh_plonk_session_shamir_pairs: negative threshold");
+        const cgh_plonk_session* s = plonk_session(session, "cgh_plonk_session_shamir_pairs");
+        *out_pairs = plonk_shamir_pairs(s->res->z, with_blinding != 0);
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
 }
 
 }  // extern "C"

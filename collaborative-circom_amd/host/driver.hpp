@@ -148,6 +148,23 @@ public:
         pre_on_host = true;
     }
     static constexpr size_t SHAMIR_BATCH = 1024;                                     // ShamirRng::BATCH_SIZE
+    // what a proof did with the pair buffers (cgh_plonk_*_shamir_party's pair_stats): pairs popped, lazy buffer_triples batches made by
+    // get_pair, pairs read from the device-resident block without passing through the host
+    size_t pairs_consumed = 0, lazy_batches = 0, pairs_from_device = 0;
+    // ONE page-locked block for the messages of the Shamir vector protocols (degree_reduce_vec, mul_open_vec), grown to the longest
+    // vector seen: every copy through it is synchronous, so the next call may reuse it (a block per call used to stay until shutdown)
+    Fr* sh_stage = nullptr; size_t sh_stage_n = 0;
+    Fr* shamir_stage(size_t n) {
+        if (n > sh_stage_n) { if (sh_stage) { CG(cg_host_free(sh_stage)); sh_stage = nullptr; sh_stage_n = 0; } void* p; CG(cg_host_alloc(std::max<size_t>(n, 1) * 32, &p)); sh_stage = (Fr*)p; sh_stage_n = n; }
+        return sh_stage;
+    }
+    // device buffers of one protocol step, released when it ends (also when a network or randomness callback throws)
+    struct DevTmp { HipDriver& d; std::vector<void*> v; explicit DevTmp(HipDriver& drv) : d(drv) {} void* get(size_t bytes) { v.push_back(d.dalloc(bytes)); return v.back(); }
+                    ~DevTmp() { if (!v.empty()) cg_dev_free_many(d.ctx, v.data(), v.size()); } };
+    // ShamirCore::share of `len` device-resident secrets for every receiver in one launch (cg_shamir_share_dev)
+    void share_dev(const void* secrets, const void* coeffs, int64_t coeff_off, int64_t coeff_stride, size_t len, int degree, const std::vector<void*>& outs, int64_t out_off, int64_t out_stride) {
+        CG(cg_shamir_share_dev(ctx, curve.id, secrets, coeffs, coeff_off, coeff_stride, len, degree, (int32_t)outs.size(), outs.data(), out_off, out_stride));
+    }
     // Shamir with the caller's own RNG (cgh_session_prove_shamir_party): every draw goes through the callback instead of the stream rng1
     const cgh_shamir_rand* sh_rand = nullptr;
     // ... or from a ChaCha12 generator seeded by the caller for this proof (cgh_session_prove_shamir_party_seeded).  ShamirProtocol's RNG is
@@ -182,8 +199,12 @@ public:
         mul_lagrange_2t = lagrange_from_coeff(p);
     }
     std::vector<Fr> shamir_share(const Fr& secret, int degree) {                       // shamir_core.rs:8-31
-        const int np = snet->num_parties();
         std::vector<Fr> coeffs; for (int k = 0; k < degree; k++) coeffs.push_back(next_rand());
+        return shamir_share(secret, coeffs.data(), degree);
+    }
+    std::vector<Fr> shamir_share(const Fr& secret, const Fr* coeffs_in, int degree) {  // the same with the coefficients already drawn
+        const int np = snet->num_parties();
+        const std::vector<Fr> coeffs(coeffs_in, coeffs_in + degree);
         std::vector<Fr> shares;
         for (int pidx = 1; pidx <= np; pidx++) {
             Fr sh = secret; const Fr x = fr_from_u64(curve, (uint64_t)pidx); Fr xp = x;
@@ -206,10 +227,14 @@ public:
     }
     void buffer_triples(size_t amount) {                                               // shamir.rs:923-1010
         const int np = snet->num_parties(), me = snet->id();
-        std::vector<Fr> rnd; for (size_t k = 0; k < amount; k++) rnd.push_back(next_rand());
+        // the reference's draw order — amount secrets, then per secret t + 2t coefficients — taken in ONE call of the randomness source
+        // (a callback per draw cost a lazily fed proof millions of calls)
+        const size_t t3 = 3 * (size_t)sh_t;
+        std::vector<Fr> rnd(amount * (1 + t3)); shamir_draw(rnd.size(), rnd.data());
         std::vector<std::vector<Fr>> send(np);
-        for (const Fr& r : rnd) {
-            auto a = shamir_share(r, sh_t), b = shamir_share(r, 2 * sh_t);
+        for (size_t k = 0; k < amount; k++) {
+            const Fr* co = rnd.data() + amount + k * t3;
+            auto a = shamir_share(rnd[k], co, sh_t), b = shamir_share(rnd[k], co + sh_t, 2 * sh_t);
             for (int to = 0; to < np; to++) { send[to].push_back(a[to]); send[to].push_back(b[to]); }
         }
         for (int to = 0; to < np; to++) if (to != me) snet->send(to, send[to].data(), send[to].size() * 32);
@@ -254,21 +279,13 @@ public:
         const Fr one = fr_from_u64(curve, 1);
         std::vector<void*> d_got(np);
         for (int from = 0; from < np; from++) d_got[from] = dalloc(2 * amount * 32);
-        void* d_pairs = dalloc(2 * amount * 32);
         Fr* const buf = mask_scratch(2 * amount);                                      // page-locked staging (parked by the host cache between proofs): the copies are plain DMA
-        for (int to = 0; to < np; to++) {                                              // ShamirCore::share for the receiver's point to + 1
-            void* dst = to == me ? d_got[me] : d_pairs;
-            const Fr x = fr_from_u64(curve, (uint64_t)to + 1);
-            std::vector<Term> a{{d_rnd, 0, 1, one}}, b{{d_rnd, 0, 1, one}};
-            Fr xp = x;
-            for (int d = 0; d < 2 * t; d++) {
-                if (d < t) a.push_back({d_rnd, (int64_t)amount + d, 3 * t, xp});
-                b.push_back({d_rnd, (int64_t)amount + t + d, 3 * t, xp});
-                xp = fr_mul(curve, xp, x);
-            }
-            lincomb(dst, 0, 2, amount, a); lincomb(dst, 1, 2, amount, b);
-            if (to != me) { CG(cg_dev_download(ctx, buf, d_pairs, 2 * amount * 32)); snet->send(to, buf, 2 * amount * 32); }
-        }
+        // ShamirCore::share for every receiver's point in two launches (degree t into the even, degree 2t into the odd entries): secret k's
+        // coefficients are draws amount + 3t k .. + 3t - 1, read where they lie.  Receiver `to`'s message is built in d_got[to], which is
+        // overwritten by what `to` sends back once it has left.
+        share_dev(d_rnd, d_rnd, (int64_t)amount, 3 * t, amount, t, d_got, 0, 2);
+        share_dev(d_rnd, d_rnd, (int64_t)amount + t, 3 * t, amount, 2 * t, d_got, 1, 2);
+        for (int to = 0; to < np; to++) if (to != me) { CG(cg_dev_download(ctx, buf, d_got[to], 2 * amount * 32)); snet->send(to, buf, 2 * amount * 32); }
         mk.mark("share+send");
         for (int from = 0; from < np; from++) if (from != me) { snet->recv(from, buf, 2 * amount * 32); CG(cg_dev_upload(ctx, d_got[from], buf, 2 * amount * 32)); check_received_dev(d_got[from], 2 * amount); }
         mk.mark("recv+upload");
@@ -286,11 +303,12 @@ public:
         pre_base = sh_r_t.size(); pre_n = outn; d_pre_rt = d_rt; d_pre_r2t = d_r2t; pre_on_host = false;
         sh_r_t.resize(pre_base + outn); sh_r_2t.resize(pre_base + outn);
         for (void* q : d_got) CG(cg_dev_free(ctx, q));
-        CG(cg_dev_free(ctx, d_rnd)); CG(cg_dev_free(ctx, d_pairs));
+        CG(cg_dev_free(ctx, d_rnd));
         mk.mark("vandermonde+free");
     }
     std::pair<Fr, Fr> get_pair() {                                                     // shamir.rs:1012-1025 (LIFO)
-        if (sh_r_t.empty()) { release_pre(); buffer_triples(SHAMIR_BATCH); }
+        if (sh_r_t.empty()) { release_pre(); buffer_triples(SHAMIR_BATCH); lazy_batches++; }
+        pairs_consumed++;
         const size_t idx = sh_r_t.size() - 1;
         if (!pre_on_host && idx >= pre_base && idx < pre_base + pre_n) {
             CG(cg_dev_download(ctx, &sh_r_t[idx], (const Fr*)d_pre_rt + (idx - pre_base), 32)); CG(cg_dev_download(ctx, &sh_r_2t[idx], (const Fr*)d_pre_r2t + (idx - pre_base), 32));
@@ -309,7 +327,8 @@ public:
         const Fr one = fr_from_u64(curve, 1);
         std::vector<Fr> rt, r2t;
         Marks mk(me == 0 ? "degree_reduce_vec king" : "degree_reduce_vec party 1", me <= 1);
-        void* tmp = dalloc(len * 32);
+        DevTmp held(*this);                                                            // released when the step ends, also when a callback fails
+        void* tmp = held.get(len * 32);
         if (on_dev) {
             lincomb(local.c[0], 0, 1, len, {{local.c[0], 0, 1, one}, {d_pre_r2t, (int64_t)(top - 1 - pre_base), -1, one}});   // input += r_2t
         } else {
@@ -319,7 +338,7 @@ public:
             CG(cg_dev_upload(ctx, tmp, r2t.data(), len * 32));
             CG(cg_vec_add_dev(ctx, curve.id, local.c[0], local.c[0], tmp, len));      // input += r_2t
         }
-        Fr* const buf = mask_scratch(len);                                             // page-locked staging of the messages to / from the king
+        Fr* const buf = shamir_stage(len);                                             // page-locked staging of the messages to / from the king
         mk.mark("add r_2t");
         if (me == 0) {                                                                 // KING_ID: interpolate at 0 from parties 0..2t, re-share with degree t
             CG(cg_vec_affine_dev(ctx, curve.id, local.c[0], local.c[0], len, mul_lagrange_2t[0].v, nullptr));   // acc = input * lagrange_0
@@ -330,39 +349,26 @@ public:
                 CG(cg_vec_add_dev(ctx, curve.id, local.c[0], local.c[0], tmp, len));
             }
             mk.mark("recv+interpolate");
-            // ShamirCore::share per element: coefficients are drawn element by element (t per element)
-            std::vector<void*> d_coeff(sh_t);
-            for (int d = 0; d < sh_t; d++) d_coeff[d] = dalloc(len * 32);
-            if (sh_gen_on && len * (size_t)sh_t >= DEVICE_MASKS_MIN) {
-                // the party's own ChaCha12 stream: draw k * t + d is coefficient d of element k — all len * t draws on the device, then de-interleaved
-                void* d_all = dalloc(len * (size_t)sh_t * 32); uint64_t after = 0;
-                CG(cg_chacha12_fr_rand_dev(ctx, curve.id, (const uint8_t*)sh_gen.key, sh_gen.word_pos, len * (size_t)sh_t, d_all, &after));
-                sh_gen.word_pos = after;
-                for (int d = 0; d < sh_t; d++) CG(cg_vec_gather_strided_dev(ctx, curve.id, d_coeff[d], d_all, len, (size_t)d, (size_t)sh_t));
-                CG(cg_dev_free(ctx, d_all));
-            } else {
-                std::vector<std::vector<Fr>> coeff(sh_t, std::vector<Fr>(len));
-                for (size_t k = 0; k < len; k++) for (int d = 0; d < sh_t; d++) coeff[d][k] = next_rand();
-                for (int d = 0; d < sh_t; d++) CG(cg_dev_upload(ctx, d_coeff[d], coeff[d].data(), len * 32));
-            }
-            void* share = dalloc(len * 32); void* term = dalloc(len * 32);
-            void* mine = dalloc(len * 32);
-            for (int to = np - 1; to >= 0; to--) {                                     // any order: every share is a function of (acc, coeffs) only
-                const Fr x = fr_from_u64(curve, (uint64_t)to + 1); Fr xp = x;
-                // share = acc + sum_d coeff_d * x^(d+1)
-                bool first = true;
-                for (int d = 0; d < sh_t; d++) {
-                    CG(cg_vec_affine_dev(ctx, curve.id, term, d_coeff[d], len, xp.v, nullptr));     // term = coeff_d * x^(d+1)
-                    CG(cg_vec_add_dev(ctx, curve.id, share, first ? local.c[0] : share, term, len));
-                    first = false; xp = fr_mul(curve, xp, x);
+            // ShamirCore::share per element: coefficients are drawn element by element (t per element) — draw k * t + d is coefficient d of
+            // element k, and the share kernel reads them in that layout: all np shares in one launch, the king's own in place
+            void* d_all = nullptr;
+            if (sh_t) {
+                d_all = held.get(len * (size_t)sh_t * 32);
+                if (sh_gen_on && len * (size_t)sh_t >= DEVICE_MASKS_MIN) {             // the party's own ChaCha12 stream, drawn on the device
+                    uint64_t after = 0;
+                    CG(cg_chacha12_fr_rand_dev(ctx, curve.id, (const uint8_t*)sh_gen.key, sh_gen.word_pos, len * (size_t)sh_t, d_all, &after));
+                    sh_gen.word_pos = after;
+                } else {
+                    std::vector<Fr> coeff(len * (size_t)sh_t);
+                    shamir_draw(coeff.size(), coeff.data());
+                    CG(cg_dev_upload(ctx, d_all, coeff.data(), coeff.size() * 32));
                 }
-                if (sh_t == 0) { CG(cg_dev_memset_zero(ctx, share, len * 32)); CG(cg_vec_add_dev(ctx, curve.id, share, share, local.c[0], len)); }
-                if (to == 0) { CG(cg_dev_memset_zero(ctx, mine, len * 32)); CG(cg_vec_add_dev(ctx, curve.id, mine, mine, share, len)); }
-                else { CG(cg_dev_download(ctx, buf, share, len * 32)); snet->send(to, buf, len * 32); }
             }
-            CG(cg_dev_free(ctx, local.c[0])); local.c[0] = mine;
-            for (void* p : d_coeff) CG(cg_dev_free(ctx, p));
-            CG(cg_dev_free(ctx, share)); CG(cg_dev_free(ctx, term));
+            std::vector<void*> outs(np);
+            outs[0] = local.c[0];
+            for (int to = 1; to < np; to++) outs[to] = held.get(len * 32);
+            share_dev(local.c[0], d_all, 0, sh_t, len, sh_t, outs, 0, 1);
+            for (int to = np - 1; to >= 1; to--) { CG(cg_dev_download(ctx, buf, outs[to], len * 32)); snet->send(to, buf, len * 32); }
             mk.mark("reshare+send");
         } else {
             if (me <= 2 * sh_t) { CG(cg_dev_download(ctx, buf, local.c[0], len * 32)); snet->send(0, buf, len * 32); }   // only if my items are required
@@ -375,9 +381,9 @@ public:
         if (on_dev) {
             lincomb(tmp, 0, 1, len, {{d_pre_rt, (int64_t)(top - 1 - pre_base), -1, one}});
             sh_r_t.resize(top - len); sh_r_2t.resize(top - len);
+            pairs_consumed += len; pairs_from_device += len;
         } else CG(cg_dev_upload(ctx, tmp, rt.data(), len * 32));
         CG(cg_vec_sub_dev(ctx, curve.id, local.c[0], local.c[0], tmp, len));          // share - r_t
-        CG(cg_dev_free(ctx, tmp));
         mk.mark("sub r_t");
         return local;
     }
@@ -616,7 +622,10 @@ public:
         out.c[0] = dalloc(a.n * 32);
         if (mode != Mode::Rep3) CG(cg_vec_mul_dev(ctx, curve.id, out.c[0], a.c[0], b.c[0], a.n));
         if (mode == Mode::Plain) return pm;
-        if (mode == Mode::Shamir) { if (exchange) out = degree_reduce_vec(out); return pm; }   // shamir.rs:609-623 (exchange = false: the degree-2t products)
+        if (mode == Mode::Shamir) {                                                   // shamir.rs:609-623 (exchange = false: the degree-2t products)
+            if (exchange) { try { out = degree_reduce_vec(out); } catch (...) { cg_dev_free(ctx, out.c[0]); throw; } }
+            return pm;
+        }
         void* m1 = nullptr; void* m2 = nullptr; void* m1_block = nullptr; bool m1_owned = true;
         if (rsrc) {
             if (!prefetched.empty() && prefetched.front().n == a.n) {
@@ -740,6 +749,7 @@ public:
         deferred.clear();
         if (!mask_bufs.empty()) { cg_ctx_sync(ctx); for (void* p : mask_bufs) cg_host_free(p); mask_bufs.clear(); }   // uploads from them may still be in flight
         release_rings(); release_pre();
+        if (sh_stage) { cg_host_free(sh_stage); sh_stage = nullptr; sh_stage_n = 0; }
         if (aux) { if (owns_aux) cg_ctx_destroy(aux); aux = nullptr; }
     }
     void sync_other_contexts() {                                                           // error paths: see VecGuard
@@ -761,7 +771,19 @@ public:
         return out;
     }
     ShareVec rand_vec(size_t n) {
-        if (mode == Mode::Shamir) { std::vector<Fr> r(n); for (size_t i = 0; i < n; i++) r[i] = get_pair().first; return upload_vec(r.data(), nullptr, n); }   // shamir.rs:570-573
+        if (mode == Mode::Shamir) {                                                   // shamir.rs:570-573: the r_t halves of the n pairs on top of the LIFO, top first
+            const size_t top = sh_r_t.size();
+            if (n && !pre_on_host && top >= n && top - n >= pre_base && top <= pre_base + pre_n) {   // all in the device-resident block: one launch, no value crosses PCIe
+                ShareVec v; v.n = n; v.c[0] = dalloc(n * 32);
+                lincomb(v.c[0], 0, 1, n, {{d_pre_rt, (int64_t)(top - 1 - pre_base), -1, fr_from_u64(curve, 1)}});
+                sh_r_t.resize(top - n); sh_r_2t.resize(top - n);
+                pairs_consumed += n; pairs_from_device += n;
+                return v;
+            }
+            if (n > 1) materialize_pre();                                              // (one download of the block instead of two 32-byte copies per pair)
+            std::vector<Fr> r(n); for (size_t i = 0; i < n; i++) r[i] = get_pair().first;
+            return upload_vec(r.data(), nullptr, n);
+        }
         if (mode != Mode::Rep3) throw std::runtime_error("rand_vec: REP3 / Shamir only");
         if (rsrc) { std::vector<Fr> a(n), b(n); for (size_t i = 0; i < n; i++) rsrc->random_fes(a[i], b[i]); return upload_vec(a.data(), b.data(), n); }
         if (cursor + n > rng_len) throw std::runtime_error("randomness stream exhausted");
@@ -776,18 +798,25 @@ public:
         if (mode == Mode::Plain) return out;
         if (mode == Mode::Shamir) {                                                   // degree-2t product opened from 2t + 1 shares (shamir.rs:684-711)
             // broadcast_next(2t) + reconstruction (shamir/network.rs:233-266): the Lagrange combination runs on the device
+            // messages staged in page-locked memory; from XCHG_STAGED_MIN elements on what arrives is range-checked on the device behind
+            // its upload (read before the next opening, verify_received_vectors), as mul_vec_finish does
             const int np = snet->num_parties(), me = snet->id(), num = (int)open_lagrange_2t.size();
-            std::vector<Fr> buf(n); CG(cg_dev_download(ctx, buf.data(), out, n * 32));
-            for (int sft = 1; sft < num; sft++) snet->send((me + sft) % np, buf.data(), n * 32);
-            std::vector<Term> terms{{out, 0, 1, open_lagrange_2t[0]}};
-            std::vector<void*> got;
-            for (int r = 1; r < num; r++) {
-                snet->recv((me + np - r) % np, buf.data(), n * 32); check_received(buf.data(), n);
-                void* d = dalloc(n * 32); CG(cg_dev_upload(ctx, d, buf.data(), n * 32));
-                got.push_back(d); terms.push_back({d, 0, 1, open_lagrange_2t[r]});
-            }
-            lincomb(out, 0, 1, n, terms);
-            for (void* d : got) CG(cg_dev_free(ctx, d));
+            const bool staged = n >= XCHG_STAGED_MIN;
+            DevTmp got(*this);
+            try {
+                Fr* const buf = shamir_stage(n);
+                CG(cg_dev_download(ctx, buf, out, n * 32));
+                for (int sft = 1; sft < num; sft++) snet->send((me + sft) % np, buf, n * 32);
+                std::vector<Term> terms{{out, 0, 1, open_lagrange_2t[0]}};
+                for (int r = 1; r < num; r++) {
+                    snet->recv((me + np - r) % np, buf, n * 32);
+                    if (!staged) check_received(buf, n);
+                    void* d = got.get(n * 32); CG(cg_dev_upload(ctx, d, buf, n * 32));
+                    if (staged) check_received_dev(d, n);
+                    terms.push_back({d, 0, 1, open_lagrange_2t[r]});
+                }
+                lincomb(out, 0, 1, n, terms);
+            } catch (...) { cg_dev_free(ctx, out); throw; }
             return out;
         }
         void* m1 = dalloc(n * 32); void* m2 = dalloc(n * 32);

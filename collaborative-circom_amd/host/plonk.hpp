@@ -367,21 +367,17 @@ public:
             beta = t.get_challenge();
             PlonkTranscript t2(c); t2.add_scalar(beta); gamma = t2.get_challenge();
         }
-        void* betaw = Tp(n); CG(cg_vec_fill_dev(ctx, c.id, betaw, n, beta.v)); CG(cg_vec_distribute_powers_dev(ctx, c.id, betaw, n, omega.v, one.v));
-        void* pv = Tp(n); void* sig = Tp(n);
-        const Fr kk[3] = {one, z.k1, z.k2};
-        ShareVec num, den;
-        for (int w = 0; w < 3; w++) {                                                     // :162-216
-            ShareVec f = T(n);
-            CG(cg_vec_affine_dev(ctx, c.id, pv, betaw, n, kk[w].v, gamma.v));
-            addpub_vec(f, buf[w], pv, n);
-            num = w == 0 ? f : mul(num, f, n);
-            CG(cg_vec_gather_strided_dev(ctx, c.id, sig, r.sigma_eval[w], n, 0, 4));
-            CG(cg_vec_affine_dev(ctx, c.id, pv, sig, n, beta.v, gamma.v));
-            ShareVec g = T(n);
-            addpub_vec(g, buf[w], pv, n);
-            den = w == 0 ? g : mul(den, g, n);
-        }
+        // the six factors num_w = buf_w + beta k_w omega^i + gamma, den_w = buf_w + beta sigma_w(omega^i) + gamma (:162-216) in one launch over
+        // every share component: omega^i = pw[4 i], sigma_w(omega^i) = sigma_eval[w][4 i], read where they lie.  The products keep their
+        // operands and their order (num b, den b, num c, den c), so a party's masks, pairs and messages do not move.
+        ShareVec f[3], g[3];
+        for (int w = 0; w < 3; w++) { f[w] = U(n); g[w] = U(n); }
+        { const Fr co[4] = {beta, M(beta, z.k1), M(beta, z.k2), gamma};
+          const void* sg[3] = {r.sigma_eval[0], r.sigma_eval[1], r.sigma_eval[2]};
+          const auto wires = table({&buf[0], &buf[1], &buf[2]}); const auto o = table({&f[0], &f[1], &f[2], &g[0], &g[1], &g[2]});
+          CG(cg_plonk_r2_factors_dev(ctx, c.id, k, d.public_component(), n, r.pw, 4, sg, 4, co, wires.data(), o.data())); }
+        ShareVec num = f[0], den = g[0];
+        for (int w = 1; w < 3; w++) { num = mul(num, f[w], n); den = mul(den, g[w], n); }
         ShareVec num_p = array_prod_mul(num, n), den_p = array_prod_mul(den, n);           // :218-224
         ShareVec den_i = inv_many(den_p, n);                                               // :228
         ShareVec zb = mul(num_p, den_i, n);                                                // :229

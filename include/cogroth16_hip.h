@@ -304,6 +304,13 @@ int32_t cg_vec_gather_strided_dev(cg_ctx* ctx, int32_t curve, void* d_out, const
  * degree_reduce_vec (shamir.rs:330-345) and open_many (shamir.rs:581-601).  d_out must not overlap a source it reads differently. */
 int32_t cg_vec_lincomb_dev(cg_ctx* ctx, int32_t curve, void* d_out, int64_t out_off, int64_t out_stride, size_t n, int32_t n_terms,
                            const void* const* d_src, const int64_t* src_off, const int64_t* src_stride, const void* h_coeffs);
+/* ShamirCore::share (shamir_core.rs:8-31) of `len` secrets for ALL receivers in one launch: out[p][out_off + i*out_stride] =
+ * s_i + c_1 x + .. + c_degree x^degree at x = p + 1, p < num_parties (1..64), by Horner, with c_j = d_coeffs[coeff_off + i*coeff_stride + j - 1]
+ * (the coefficients interleaved as the draws produce them, element by element: no de-interleaving pass); secrets and coefficients are
+ * read once.  The king's re-sharing in degree_reduce_vec (shamir.rs:347-365) and the sharing step of buffer_triples (shamir.rs:923-960).
+ * Offsets and strides count elements.  d_outs[p] may be d_secrets itself when out_off = 0 and out_stride = 1; degree 0 copies. */
+int32_t cg_shamir_share_dev(cg_ctx* ctx, int32_t curve, const void* d_secrets, const void* d_coeffs, int64_t coeff_off, int64_t coeff_stride, size_t len, int32_t degree,
+                            int32_t num_parties, void* const* d_outs, int64_t out_off, int64_t out_stride);
 int32_t cg_vec_prefix_prod_dev(cg_ctx* ctx, int32_t curve, void* d_out, const void* d_in, size_t n);
 int32_t cg_vec_prefix_sum_dev(cg_ctx* ctx, int32_t curve, void* d_out, const void* d_in, size_t n);
 int32_t cg_vec_inverse_dev(cg_ctx* ctx, int32_t curve, void* d_out, const void* d_in, size_t n);
@@ -319,6 +326,10 @@ int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, c
  *   additions: ext[n_priv + a] = f1 * w[id1] + f2 * w[id2] for a = d_order[0..n), one dependency level of the zkey's additions
  *              (co-plonk round1.rs:209-238); d_ids = 2 u32 per addition, d_coeffs = (f1, f2) per addition; w[id] = d_pub[id] in
  *              public_component for id < n_inputs (zero elsewhere), else ext[id - n_inputs].  d_ext_b NULL = one component.
+ *   r2_factors: the six factors of round 2's grand product on the n-point domain (round2.rs:162-216): num_w = w + beta k_w omega^i + gamma,
+ *              den_w = w + beta sigma_w(omega^i) + gamma; omega^i = d_pw[i * pw_stride], sigma_w(omega^i) = d_sigma[w][i * sigma_stride] (the
+ *              zkey's 4n evaluations are read with a stride of 4); h_coeffs = beta, beta k1, beta k2, gamma; d_wires = 3 x 2 (the wire
+ *              buffers a, b, c); d_out = 6 x 2 (num_a, num_b, num_c, den_a, den_b, den_c).
  *   r3_blind:  the round-3 blinding vectors ap, bp, cp, zp, zwp (round3.rs:246-256, 307-322) from pw[i] = omega4^i; h_blind = k x 9
  *              elements (b_1..b_9 of each component); d_out = 5 x 2.
  *   r3_perm:   fa, fb, fc (a + beta k x + gamma) and ga, gb, gc (a + beta sigma + gamma) (round3.rs:370-418); h_coeffs = beta,
@@ -334,6 +345,8 @@ int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, c
  *              (round3.rs:443-453); n = the domain size; d_t, d_tz = 2 each. */
 int32_t cg_plonk_additions_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_order, size_t n, const uint32_t* d_ids, const void* d_coeffs, const void* d_pub,
                                uint32_t n_inputs, int32_t public_component, void* d_ext_a, void* d_ext_b, size_t n_priv);
+int32_t cg_plonk_r2_factors_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_pw, size_t pw_stride, const void* const* d_sigma,
+                                size_t sigma_stride, const void* h_coeffs, const void* const* d_wires, void* const* d_out);
 int32_t cg_plonk_r3_blind_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, const void* d_pw, const void* h_omega, const void* h_blind, void* const* d_out);
 int32_t cg_plonk_r3_perm_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_pw, const void* const* d_sigma,
                              const void* h_coeffs, const void* const* d_wires, void* const* d_out);

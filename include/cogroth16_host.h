@@ -270,6 +270,18 @@ int32_t cgh_plonk_prove_rep3_party_ex(int32_t device, int32_t curve, const char*
 int32_t cgh_plonk_prove_shamir(int32_t device, int32_t curve, const char* zkey_path, int32_t n, int32_t t, const uint64_t* pub_in, const uint64_t* const* wit,
                                const uint64_t* const* blind, const uint64_t* const* streams, size_t stream_len, int32_t upto,
                                uint64_t* out_commits, uint64_t* out_evals, uint64_t* out_challenges);
+/* ONE Shamir party of co-plonk: party net->party_id of net->num_parties with threshold t (2t + 1 <= n), the caller's any-to-any network and
+ * private randomness (tables of cgh_session_prove_shamir_party); the messages are those of cgh_plonk_prove_shamir (shamir.rs:302-384, 570-573,
+ * 684-711 under co-plonk/src/plonk.rs:133-271).  wit = this party's shares of the private witness; blind = its shares of b_1..b_11, or
+ * NULL to draw them with rand() first (round1.rs:93-99), after the preprocessing.  preprocess = double-sharing batches generated up front on
+ * the GPU (ShamirProtocol::preprocess, shamir.rs:248-250; each yields t + 1 pairs), 0 = the reference's lazy batches of 1024.  upto = 1..5.
+ * Outputs as the REP3 party entry; seconds = wall time of the proof, preprocessing included; optional:
+ *   round_seconds[6]  wall time of the preprocessing and of rounds 1..5 (the stream is drained once per round only when this is given);
+ *   pair_stats[4]     pairs consumed by the proof, pairs left in the buffers at return, lazy buffer_triples batches made, pairs read from the
+ *                     device-resident preprocessed block without passing through the host. */
+int32_t cgh_plonk_prove_shamir_party(int32_t device, int32_t curve, const char* zkey_path, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind,
+                                     const cgh_shamir_net* net, const cgh_shamir_rand* rnd, size_t preprocess, int32_t upto, uint64_t* out_commits, uint64_t* out_evals,
+                                     uint64_t* out_challenges, double* seconds, double* round_seconds, size_t* pair_stats);
 /* co-plonk proving sessions: the zkey is read once; p_tau is registered (validated unless flags has CGH_SESSION_SKIP_VALIDATION, given
  * per-window tables as precompute asks: < 0 = chosen by size, 0 = none, c = window) and the q, sigma and Lagrange polynomials, the wire maps,
  * the omega4^i table of round 3 and the additions' level schedule stay on the device until close (co-circom.rs:546-590 reads the zkey
@@ -285,6 +297,20 @@ int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in
                                            const uint64_t* blind_a, const uint64_t* blind_b, const cgh_rep3_net* net,
                                            const cgh_rep3_rand* rnd, const cgh_rep3_chacha* streams,
                                            uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds);
+/* The Shamir party on a session (rounds 1..5; arguments as cgh_plonk_prove_shamir_party), and the same party with its private randomness
+ * as ONE 32-byte seed: the library's own ChaCha12 stream, the large draws (preprocessing, the king's re-sharing coefficients) made on the GPU
+ * by cg_chacha12_fr_rand_dev, as cgh_session_prove_shamir_party_seeded does.  A failing callback ends the call with a status and a
+ * cgh_last_error text; the session stays usable. */
+int32_t cgh_plonk_session_prove_shamir_party(void* session, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind, const cgh_shamir_net* net,
+                                             const cgh_shamir_rand* rnd, size_t preprocess, uint64_t* commits, uint64_t* evals, uint64_t* challenges,
+                                             double* seconds, double* round_seconds, size_t* pair_stats);
+int32_t cgh_plonk_session_prove_shamir_party_seeded(void* session, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit, const uint64_t* blind, const cgh_shamir_net* net,
+                                                    const uint8_t* seed32, size_t preprocess, uint64_t* commits, uint64_t* evals, uint64_t* challenges,
+                                                    double* seconds, double* round_seconds, size_t* pair_stats);
+/* The exact number of double-sharing pairs one proof on this session consumes: 158 n + 4 for a domain of n rows (round 2: 14 n + 4, round 3:
+ * 36 products of 4 n elements), + 11 when the blindings are drawn inside (with_blinding != 0).  It depends on the zkey through the domain
+ * size only (not on n_public or on the threshold).  The `preprocess` that covers a proof is ceil(out_pairs / (threshold + 1)). */
+int32_t cgh_plonk_session_shamir_pairs(void* session, int32_t threshold, int32_t with_blinding, size_t* out_pairs);
 /* Keccak256 transcript (co-plonk/src/types.rs:102-227): kinds[i] 0 = scalar, 1 = packed G1 point; out = the challenge */
 int32_t cgh_plonk_transcript(int32_t curve, const int32_t* kinds, const uint64_t* const* payloads, int32_t n_items, uint64_t* out_challenge);
 
