@@ -30,10 +30,9 @@ int32_t cgh_prove_shamir(int32_t device, int32_t curve, const char* zkey_path, i
                 InProcShamirNet net(&hub, i);
                 HipDriver driver(ctx, z.curve, Mode::Shamir, nullptr);
                 driver.use_second_context(second.take(i));
-                driver.rng1 = (const Fr*)streams[i]; driver.rng_len = stream_len;
-                driver.shamir_init(&net, t);
+                driver.become_shamir_party(&net, t, ShamirRandom((const Fr*)streams[i], stream_len));
                 const auto ta = std::chrono::steady_clock::now();
-                driver.preprocess(preprocess);                                            // 0 = the reference's lazy batches of 1024
+                driver.sh.preprocess(preprocess);                                         // 0 = the reference's lazy batches of 1024
                 const auto tb = std::chrono::steady_clock::now();
                 ShareVec w = driver.upload_vec((const Fr*)wit[i], nullptr, n_aux);
                 CoGroth16 prover(driver);

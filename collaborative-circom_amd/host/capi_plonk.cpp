@@ -103,14 +103,6 @@ void plonk_prove_rep3_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, const
 //   blindings drawn inside        11             b_1..b_11 with rand() (round1.rs:93-99)
 // = 158 n + 4 (+ 11).  It depends on the zkey through the domain size only: neither n_public, the additions nor the threshold enter.
 size_t plonk_shamir_pairs(const cgh::PlonkZKey& z, bool with_blinding) { return 158 * z.domain_size + 4 + (with_blinding ? 11 : 0); }
-// what the three party entries refuse before a session, a file or a device is looked at
-void shamir_party_args(const char* who, int32_t threshold, const cgh_shamir_net* net, const cgh_shamir_rand* rnd, const uint8_t* seed32, const void* pub_in, const void* wit, const void* commits) {
-    const std::string w(who);
-    if (!pub_in || !wit || !net || (!rnd && !seed32) || !commits) throw std::runtime_error(w + ": null argument");
-    if (rnd && !rnd->random_field_elements) throw std::runtime_error("cgh_shamir_rand: random_field_elements is required");
-    if (net->num_parties < 3) throw std::runtime_error(w + ": Shamir protocol requires at least 3 parties");
-    if (threshold < 0 || 2 * (int64_t)threshold + 1 > net->num_parties) throw std::runtime_error(w + ": Threshold too large for number of parties");
-}
 // round_seconds[6]: preprocessing, rounds 1..5 (round 1 includes drawing the blindings and the witness upload); pair_stats[4]: pairs
 // consumed, pairs left, lazy buffer_triples batches, pairs read from the device-resident block
 void plonk_prove_shamir_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, int32_t threshold, const uint64_t* pub_in, const uint64_t* wit_in, const uint64_t* blind,
@@ -121,12 +113,10 @@ void plonk_prove_shamir_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, int
     std::vector<Fr> pub((const Fr*)pub_in, (const Fr*)pub_in + z.n_public + 1);
     CallbackShamirNet net(*net_cb);
     HipDriver driver(ctx, z.curve, Mode::Shamir, nullptr);
-    driver.sh_rand = rnd_cb;
-    if (seed32) { driver.sh_gen = ChaCha12(seed32); driver.sh_gen_on = true; }
-    driver.shamir_init(&net, threshold);                                               // ShamirProtocol::new, shamir.rs:211-246
+    driver.become_shamir_party(&net, threshold, ShamirRandom(rnd_cb, seed32));         // ShamirProtocol::new, shamir.rs:211-246
     if (round_seconds) for (int i = 0; i < 6; i++) round_seconds[i] = 0;
     const auto t0 = std::chrono::steady_clock::now();
-    driver.preprocess(preprocess);                                                     // shamir.rs:248-250; 0 = lazy batches of 1024
+    driver.sh.preprocess(preprocess);                                                  // shamir.rs:248-250; 0 = lazy batches of 1024
     if (round_seconds) { CG(cg_ctx_sync(ctx)); round_seconds[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
     FieldShare b[11];
     for (int q = 0; q < 11; q++) {
@@ -137,7 +127,7 @@ void plonk_prove_shamir_party_on(cg_ctx* ctx, const cgh::PlonkResident& res, int
     try { plonk_run(driver, res, pub, wit, b, upto, o, round_seconds ? round_seconds + 1 : nullptr); }
     catch (...) { driver.free_vec(wit); throw; }
     driver.free_vec(wit);
-    if (pair_stats) { pair_stats[0] = driver.pairs_consumed; pair_stats[1] = driver.sh_r_t.size(); pair_stats[2] = driver.lazy_batches; pair_stats[3] = driver.pairs_from_device; }
+    if (pair_stats) { const PairStack& ps = driver.sh.pairs; pair_stats[0] = ps.consumed; pair_stats[1] = ps.size(); pair_stats[2] = ps.lazy_batches; pair_stats[3] = ps.from_device; }
 }
 }  // namespace
 // PlainHipDriver through rounds 1..upto (<= 5).  full_witness = n_vars - n_additions Montgomery elements (Groth16-style, leading one);
@@ -198,8 +188,7 @@ int32_t cgh_plonk_prove_shamir(int32_t device, int32_t curve, const char* zkey_p
                 InProcShamirNet net(&hub, i);
                 {
                     HipDriver driver(ctx, c, Mode::Shamir, nullptr);
-                    driver.rng1 = (const Fr*)streams[i]; driver.rng_len = stream_len;
-                    driver.shamir_init(&net, t);
+                    driver.become_shamir_party(&net, t, ShamirRandom((const Fr*)streams[i], stream_len));
                     ShareVec w = driver.upload_vec((const Fr*)wit[i], nullptr, n_priv);
                     FieldShare b[11]; for (int q = 0; q < 11; q++) { memcpy(b[q].c[0].v, blind[i] + 4 * q, 32); b[q].c[1] = b[q].c[0]; }
                     plonk_run(driver, *res, pub, w, b, upto, PlonkOut{(uint64_t*)((uint8_t*)out_commits + (size_t)i * 9 * psz), out_challenges ? out_challenges + i * 20 : nullptr,

@@ -82,18 +82,13 @@ struct MultiDevice { std::vector<WorkerDevice> workers; };
 
 enum class Mode { Plain, Rep3, Shamir };
 
-class HipDriver {
-public:
-    cg_ctx* ctx; Curve curve; Mode mode; Rep3Network* net;
-    const Fr* rng1 = nullptr; const Fr* rng2 = nullptr; size_t rng_len = 0, cursor = 0;   // rngs.rs:25-46 streams (inputs)
-    // REP3 with the caller's own Rep3Rand (cgh_session_prove_rep3_party): every draw goes through it instead of the two arrays above
-    Rep3RandSource* rsrc = nullptr;
+// What the protocol steps of both sharings use of the device — context and curve, scratch that lives until shutdown, the checks of what a
+// peer sent, linear combinations, timing marks — apart from any protocol state: HipDriver is built on it, and so is ShamirParty (shamir.hpp)
+struct DriverBase {
+    cg_ctx* ctx; Curve curve;
+    DriverBase(cg_ctx* c, Curve cv) : ctx(c), curve(cv) {}
     std::vector<void*> mask_bufs;                                                          // page-locked scratch lent to rsrc, released at shutdown
     Fr* mask_scratch(size_t n) { void* p; CG(cg_host_alloc(n * 32, &p)); mask_bufs.push_back(p); return (Fr*)p; }
-    int k() const { return k_override ? k_override : (mode == Mode::Rep3 ? 2 : 1); }
-    // REP3 "additive quotient" variant (opt-in, NOT the reference's message sequence; see CoGroth16::prove): vector work on the own component only
-    int k_override = 0; bool additive_h = false;
-    struct Components { HipDriver& d; int old; Components(HipDriver& drv, int kk) : d(drv), old(drv.k_override) { d.k_override = kk; } ~Components() { d.k_override = old; } };
     // What arrives from a peer is checked the way the reference's deserialisation checks it (ark-serialize Validate::Yes behind
     // mpc-net's recv, rep3/network.rs:137-176 / shamir/network.rs:159-213): points on the curve and in the subgroup, field elements
     // below the modulus; failure = InvalidData.  (The 2 x m-element exchanges of mul_vec go to the device unchecked: DESIGN.md §4.)
@@ -118,9 +113,6 @@ public:
         int32_t ok = 0; CG(cg_fr_is_canonical(curve.id, elements, n, &ok));
         if (!ok) throw std::runtime_error("invalid data: a field element received from a peer is not below the modulus");
     }
-    int party() const { return mode == Mode::Rep3 ? net->id() : -1; }
-
-    HipDriver(cg_ctx* c, Curve cv, Mode m, Rep3Network* n) : ctx(c), curve(cv), mode(m), net(n) {}
     // CGH_TIMING=1: wall-clock marks of the host-side protocol steps (stderr, microseconds since the previous mark)
     struct Marks {
         bool on; const char* what; std::chrono::steady_clock::time_point last; std::string line;
@@ -132,120 +124,10 @@ public:
         }
         ~Marks() { if (on) fprintf(stderr, "%s [us]:%s\n", what, line.c_str()); }
     };
-
-    // ---- Shamir state (shamir.rs:196-246): threshold, Lagrange tables, buffered double sharings; randomness = stream rng1
-    ShamirNet* snet = nullptr; int sh_t = 0;
-    std::vector<Fr> open_lagrange_t, open_lagrange_2t, mul_lagrange_2t;
-    FrLazyVec sh_r_t, sh_r_2t;                                                           // LIFO pair buffers (shamir.rs:873-880); resize() does not touch the new elements
-    // preprocessed pairs stay on the device: entries [pre_base, pre_base + pre_n) of the two buffers above are held in d_pre_* and
-    // copied to the host only when a scalar pop or the lazy path needs them
-    void* d_pre_rt = nullptr; void* d_pre_r2t = nullptr; size_t pre_base = 0, pre_n = 0; bool pre_on_host = true;
-    void release_pre() { if (d_pre_rt) { cg_dev_free(ctx, d_pre_rt); cg_dev_free(ctx, d_pre_r2t); d_pre_rt = d_pre_r2t = nullptr; } pre_n = 0; pre_on_host = true; }
-    void materialize_pre() {
-        if (pre_on_host) return;
-        const size_t live = std::min(pre_n, sh_r_t.size() > pre_base ? sh_r_t.size() - pre_base : 0);
-        if (live) { CG(cg_dev_download(ctx, sh_r_t.data() + pre_base, d_pre_rt, live * 32)); CG(cg_dev_download(ctx, sh_r_2t.data() + pre_base, d_pre_r2t, live * 32)); }
-        pre_on_host = true;
-    }
-    static constexpr size_t SHAMIR_BATCH = 1024;                                     // ShamirRng::BATCH_SIZE
-    // what a proof did with the pair buffers (cgh_plonk_*_shamir_party's pair_stats): pairs popped, lazy buffer_triples batches made by
-    // get_pair, pairs read from the device-resident block without passing through the host
-    size_t pairs_consumed = 0, lazy_batches = 0, pairs_from_device = 0;
-    // ONE page-locked block for the messages of the Shamir vector protocols (degree_reduce_vec, mul_open_vec), grown to the longest
-    // vector seen: every copy through it is synchronous, so the next call may reuse it (a block per call used to stay until shutdown)
-    Fr* sh_stage = nullptr; size_t sh_stage_n = 0;
-    Fr* shamir_stage(size_t n) {
-        if (n > sh_stage_n) { if (sh_stage) { CG(cg_host_free(sh_stage)); sh_stage = nullptr; sh_stage_n = 0; } void* p; CG(cg_host_alloc(std::max<size_t>(n, 1) * 32, &p)); sh_stage = (Fr*)p; sh_stage_n = n; }
-        return sh_stage;
-    }
+    void* dalloc(size_t bytes) { void* p; CG(cg_dev_alloc(ctx, bytes, &p)); return p; }
     // device buffers of one protocol step, released when it ends (also when a network or randomness callback throws)
-    struct DevTmp { HipDriver& d; std::vector<void*> v; explicit DevTmp(HipDriver& drv) : d(drv) {} void* get(size_t bytes) { v.push_back(d.dalloc(bytes)); return v.back(); }
-                    ~DevTmp() { if (!v.empty()) cg_dev_free_many(d.ctx, v.data(), v.size()); } };
-    // ShamirCore::share of `len` device-resident secrets for every receiver in one launch (cg_shamir_share_dev)
-    void share_dev(const void* secrets, const void* coeffs, int64_t coeff_off, int64_t coeff_stride, size_t len, int degree, const std::vector<void*>& outs, int64_t out_off, int64_t out_stride) {
-        CG(cg_shamir_share_dev(ctx, curve.id, secrets, coeffs, coeff_off, coeff_stride, len, degree, (int32_t)outs.size(), outs.data(), out_off, out_stride));
-    }
-    // Shamir with the caller's own RNG (cgh_session_prove_shamir_party): every draw goes through the callback instead of the stream rng1
-    const cgh_shamir_rand* sh_rand = nullptr;
-    // ... or from a ChaCha12 generator seeded by the caller for this proof (cgh_session_prove_shamir_party_seeded).  ShamirProtocol's RNG is
-    // PRIVATE (`RngType::from_entropy()`, shamir.rs:211-246: no peer reproduces its draws), so a generator the library positions itself is
-    // as good as the caller's: the amount * (1 + 3t) draws of `preprocess` are then made on the device, the short ones here, one stream.
-    ChaCha12 sh_gen; bool sh_gen_on = false;
-    void shamir_draw(size_t n, Fr* out) {
-        if (sh_gen_on) { for (size_t i = 0; i < n; i++) sh_gen.fr_rand(MOD_R[curve.id], curve.id == CG_BN254 ? 254 : 255, out[i].v); return; }
-        if (sh_rand) { if (const int32_t rc = sh_rand->random_field_elements(sh_rand->user, n, (uint64_t*)out)) throw std::runtime_error("randomness source: random_field_elements failed with code " + std::to_string(rc)); return; }
-        if (cursor + n > rng_len) throw std::runtime_error("randomness stream exhausted");
-        memcpy(out, rng1 + cursor, n * 32); cursor += n;
-    }
-    Fr next_rand() { Fr x; shamir_draw(1, &x); return x; }
-    std::vector<Fr> lagrange_from_coeff(const std::vector<size_t>& pts) const {       // shamir_core.rs:56-75
-        std::vector<Fr> res;
-        for (size_t i : pts) {
-            Fr num = fr_from_u64(curve, 1), den = num; const Fr fi = fr_from_u64(curve, i);
-            for (size_t j : pts) if (i != j) { const Fr fj = fr_from_u64(curve, j); num = fr_mul(curve, num, fj); den = fr_mul(curve, den, fr_sub(curve, fj, fi)); }
-            res.push_back(fr_mul(curve, num, fr_inv(curve, den)));
-        }
-        return res;
-    }
-    void shamir_init(ShamirNet* n, int threshold) {                                    // ShamirProtocol::new, shamir.rs:211-246
-        snet = n; sh_t = threshold;
-        const int np = n->num_parties(), id = n->id();
-        if (2 * threshold + 1 > np) throw std::runtime_error("Threshold too large for number of parties");
-        std::vector<size_t> p; for (int i = 0; i <= threshold; i++) p.push_back((size_t)((id + np - i) % np + 1));
-        open_lagrange_t = lagrange_from_coeff(p);
-        p.clear(); for (int i = 0; i <= 2 * threshold; i++) p.push_back((size_t)((id + np - i) % np + 1));
-        open_lagrange_2t = lagrange_from_coeff(p);
-        p.clear(); for (int i = 1; i <= 2 * threshold + 1; i++) p.push_back((size_t)i);
-        mul_lagrange_2t = lagrange_from_coeff(p);
-    }
-    std::vector<Fr> shamir_share(const Fr& secret, int degree) {                       // shamir_core.rs:8-31
-        std::vector<Fr> coeffs; for (int k = 0; k < degree; k++) coeffs.push_back(next_rand());
-        return shamir_share(secret, coeffs.data(), degree);
-    }
-    std::vector<Fr> shamir_share(const Fr& secret, const Fr* coeffs_in, int degree) {  // the same with the coefficients already drawn
-        const int np = snet->num_parties();
-        const std::vector<Fr> coeffs(coeffs_in, coeffs_in + degree);
-        std::vector<Fr> shares;
-        for (int pidx = 1; pidx <= np; pidx++) {
-            Fr sh = secret; const Fr x = fr_from_u64(curve, (uint64_t)pidx); Fr xp = x;
-            for (const Fr& cf : coeffs) { sh = fr_add(curve, sh, fr_mul(curve, xp, cf)); xp = fr_mul(curve, xp, x); }
-            shares.push_back(sh);
-        }
-        return shares;
-    }
-    void vandermonde_mul(const std::vector<Fr>& in, FrLazyVec& out) {            // shamir.rs:904-921 (appends t + 1 values)
-        const int np = snet->num_parties();
-        std::vector<Fr> row(np), cur(np);
-        for (int i = 0; i < np; i++) { row[i] = fr_from_u64(curve, (uint64_t)i + 1); cur[i] = row[i]; }
-        Fr s0 = fr_from_u64(curve, 0); for (const Fr& v : in) s0 = fr_add(curve, s0, v);
-        out.push_back(s0);
-        for (int k = 1; k <= sh_t; k++) {
-            Fr acc = fr_from_u64(curve, 0);
-            for (int i = 0; i < np; i++) { acc = fr_add(curve, acc, fr_mul(curve, cur[i], in[i])); cur[i] = fr_mul(curve, cur[i], row[i]); }
-            out.push_back(acc);
-        }
-    }
-    void buffer_triples(size_t amount) {                                               // shamir.rs:923-1010
-        const int np = snet->num_parties(), me = snet->id();
-        // the reference's draw order — amount secrets, then per secret t + 2t coefficients — taken in ONE call of the randomness source
-        // (a callback per draw cost a lazily fed proof millions of calls)
-        const size_t t3 = 3 * (size_t)sh_t;
-        std::vector<Fr> rnd(amount * (1 + t3)); shamir_draw(rnd.size(), rnd.data());
-        std::vector<std::vector<Fr>> send(np);
-        for (size_t k = 0; k < amount; k++) {
-            const Fr* co = rnd.data() + amount + k * t3;
-            auto a = shamir_share(rnd[k], co, sh_t), b = shamir_share(rnd[k], co + sh_t, 2 * sh_t);
-            for (int to = 0; to < np; to++) { send[to].push_back(a[to]); send[to].push_back(b[to]); }
-        }
-        for (int to = 0; to < np; to++) if (to != me) snet->send(to, send[to].data(), send[to].size() * 32);
-        std::vector<std::vector<Fr>> got(np);
-        for (int from = 0; from < np; from++) { if (from == me) got[from] = send[me]; else { got[from].resize(2 * amount); snet->recv(from, got[from].data(), 2 * amount * 32); check_received(got[from].data(), 2 * amount); } }
-        for (size_t k = 0; k < amount; k++) {
-            std::vector<Fr> in_t(np), in_2t(np);
-            for (int from = 0; from < np; from++) { in_t[from] = got[from][2 * k]; in_2t[from] = got[from][2 * k + 1]; }
-            vandermonde_mul(in_t, sh_r_t); vandermonde_mul(in_2t, sh_r_2t);
-        }
-    }
+    struct DevTmp { DriverBase& d; std::vector<void*> v; explicit DevTmp(DriverBase& drv) : d(drv) {} void* get(size_t bytes) { v.push_back(d.dalloc(bytes)); return v.back(); }
+                    void take(void* p) { v.erase(std::find(v.begin(), v.end(), p)); }   /* p has an owner that outlives the step */   void free_now() { if (!v.empty()) cg_dev_free_many(d.ctx, v.data(), v.size()); v.clear(); }   ~DevTmp() { free_now(); } };
     // out[off + i*stride] = sum of terms on the device (cg_vec_lincomb_dev, at most 8 terms a launch: longer sums continue on `out`)
     struct Term { const void* src; int64_t off, stride; Fr coeff; };
     void lincomb(void* out, int64_t off, int64_t stride, size_t n, const std::vector<Term>& terms) {
@@ -259,184 +141,29 @@ public:
             CG(cg_vec_lincomb_dev(ctx, curve.id, out, off, stride, n, (int32_t)part.size(), src, so, ss, cf));
         }
     }
-    // ShamirProtocol::preprocess (shamir.rs:248-250) = buffer_triples(amount) (shamir.rs:923-1010) with the share algebra on the
-    // device: the same draws from the stream in the same order (amount secrets, then per secret t + 2t coefficients), the same
-    // values appended to the pair buffers, one message per peer.  The lazily refilled batches of 1024 (get_pair) stay on the host.
-    void preprocess(size_t amount) {
-        if (!amount) return;
-        const int np = snet->num_parties(), me = snet->id(), t = sh_t;
-        const size_t draws = amount * (size_t)(1 + 3 * t);
-        if (!sh_rand && !sh_gen_on && cursor + draws > rng_len) throw std::runtime_error("randomness stream exhausted");
-        Marks mk("shamir preprocess", me == 0);
-        void* d_rnd = dalloc(draws * 32);
-        if (sh_gen_on && draws >= DEVICE_MASKS_MIN) {                                  // the same stream, drawn where it is needed
-            uint64_t after = 0;
-            CG(cg_chacha12_fr_rand_dev(ctx, curve.id, (const uint8_t*)sh_gen.key, sh_gen.word_pos, draws, d_rnd, &after));
-            sh_gen.word_pos = after;
-        } else if (sh_rand || sh_gen_on) { std::vector<Fr> tmp(draws); shamir_draw(draws, tmp.data()); CG(cg_dev_upload(ctx, d_rnd, tmp.data(), draws * 32)); }
-        else { CG(cg_dev_upload(ctx, d_rnd, rng1 + cursor, draws * 32)); cursor += draws; }
-        mk.mark("upload draws");
-        const Fr one = fr_from_u64(curve, 1);
-        std::vector<void*> d_got(np);
-        for (int from = 0; from < np; from++) d_got[from] = dalloc(2 * amount * 32);
-        Fr* const buf = mask_scratch(2 * amount);                                      // page-locked staging (parked by the host cache between proofs): the copies are plain DMA
-        // ShamirCore::share for every receiver's point in two launches (degree t into the even, degree 2t into the odd entries): secret k's
-        // coefficients are draws amount + 3t k .. + 3t - 1, read where they lie.  Receiver `to`'s message is built in d_got[to], which is
-        // overwritten by what `to` sends back once it has left.
-        share_dev(d_rnd, d_rnd, (int64_t)amount, 3 * t, amount, t, d_got, 0, 2);
-        share_dev(d_rnd, d_rnd, (int64_t)amount + t, 3 * t, amount, 2 * t, d_got, 1, 2);
-        for (int to = 0; to < np; to++) if (to != me) { CG(cg_dev_download(ctx, buf, d_got[to], 2 * amount * 32)); snet->send(to, buf, 2 * amount * 32); }
-        mk.mark("share+send");
-        for (int from = 0; from < np; from++) if (from != me) { snet->recv(from, buf, 2 * amount * 32); CG(cg_dev_upload(ctx, d_got[from], buf, 2 * amount * 32)); check_received_dev(d_got[from], 2 * amount); }
-        mk.mark("recv+upload");
-        // Vandermonde rows 1, x, .., x^t over the senders' points (shamir.rs:904-921): t + 1 outputs per secret
-        const size_t outn = amount * (size_t)(t + 1);
-        void* d_rt = dalloc(outn * 32); void* d_r2t = dalloc(outn * 32);
-        std::vector<Fr> pw(np, one);
-        for (int kk = 0; kk <= t; kk++) {
-            std::vector<Term> a, b;
-            for (int from = 0; from < np; from++) { a.push_back({d_got[from], 0, 2, pw[from]}); b.push_back({d_got[from], 1, 2, pw[from]}); }
-            lincomb(d_rt, kk, t + 1, amount, a); lincomb(d_r2t, kk, t + 1, amount, b);
-            for (int from = 0; from < np; from++) pw[from] = fr_mul(curve, pw[from], fr_from_u64(curve, (uint64_t)from + 1));
-        }
-        materialize_pre(); release_pre();                                              // an earlier preprocessed block moves to the host
-        pre_base = sh_r_t.size(); pre_n = outn; d_pre_rt = d_rt; d_pre_r2t = d_r2t; pre_on_host = false;
-        sh_r_t.resize(pre_base + outn); sh_r_2t.resize(pre_base + outn);
-        for (void* q : d_got) CG(cg_dev_free(ctx, q));
-        CG(cg_dev_free(ctx, d_rnd));
-        mk.mark("vandermonde+free");
-    }
-    std::pair<Fr, Fr> get_pair() {                                                     // shamir.rs:1012-1025 (LIFO)
-        if (sh_r_t.empty()) { release_pre(); buffer_triples(SHAMIR_BATCH); lazy_batches++; }
-        pairs_consumed++;
-        const size_t idx = sh_r_t.size() - 1;
-        if (!pre_on_host && idx >= pre_base && idx < pre_base + pre_n) {
-            CG(cg_dev_download(ctx, &sh_r_t[idx], (const Fr*)d_pre_rt + (idx - pre_base), 32)); CG(cg_dev_download(ctx, &sh_r_2t[idx], (const Fr*)d_pre_r2t + (idx - pre_base), 32));
-        }
-        std::pair<Fr, Fr> pr{sh_r_t.back(), sh_r_2t.back()};
-        sh_r_t.pop_back(); sh_r_2t.pop_back();
-        return pr;
-    }
-    // degree_reduce_vec, shamir.rs:302-384.  `local` holds this party's products on the device and is consumed.
-    ShareVec degree_reduce_vec(ShareVec local) {
-        const int np = snet->num_parties(), me = snet->id();
-        const size_t len = local.n;
-        // the len pairs on top of the LIFO buffers, top first; read straight from the device when the preprocessed block holds them all
-        const size_t top = sh_r_t.size();
-        const bool on_dev = !pre_on_host && top >= len && top - len >= pre_base && top <= pre_base + pre_n;
-        const Fr one = fr_from_u64(curve, 1);
-        std::vector<Fr> rt, r2t;
-        Marks mk(me == 0 ? "degree_reduce_vec king" : "degree_reduce_vec party 1", me <= 1);
-        DevTmp held(*this);                                                            // released when the step ends, also when a callback fails
-        void* tmp = held.get(len * 32);
-        if (on_dev) {
-            lincomb(local.c[0], 0, 1, len, {{local.c[0], 0, 1, one}, {d_pre_r2t, (int64_t)(top - 1 - pre_base), -1, one}});   // input += r_2t
-        } else {
-            materialize_pre();
-            rt.resize(len); r2t.resize(len);
-            for (size_t k = 0; k < len; k++) { auto pr = get_pair(); rt[k] = pr.first; r2t[k] = pr.second; }
-            CG(cg_dev_upload(ctx, tmp, r2t.data(), len * 32));
-            CG(cg_vec_add_dev(ctx, curve.id, local.c[0], local.c[0], tmp, len));      // input += r_2t
-        }
-        Fr* const buf = shamir_stage(len);                                             // page-locked staging of the messages to / from the king
-        mk.mark("add r_2t");
-        if (me == 0) {                                                                 // KING_ID: interpolate at 0 from parties 0..2t, re-share with degree t
-            CG(cg_vec_affine_dev(ctx, curve.id, local.c[0], local.c[0], len, mul_lagrange_2t[0].v, nullptr));   // acc = input * lagrange_0
-            for (int other = 1; other <= 2 * sh_t; other++) {
-                snet->recv(other, buf, len * 32);
-                CG(cg_dev_upload(ctx, tmp, buf, len * 32)); check_received_dev(tmp, len);
-                CG(cg_vec_affine_dev(ctx, curve.id, tmp, tmp, len, mul_lagrange_2t[other].v, nullptr));
-                CG(cg_vec_add_dev(ctx, curve.id, local.c[0], local.c[0], tmp, len));
-            }
-            mk.mark("recv+interpolate");
-            // ShamirCore::share per element: coefficients are drawn element by element (t per element) — draw k * t + d is coefficient d of
-            // element k, and the share kernel reads them in that layout: all np shares in one launch, the king's own in place
-            void* d_all = nullptr;
-            if (sh_t) {
-                d_all = held.get(len * (size_t)sh_t * 32);
-                if (sh_gen_on && len * (size_t)sh_t >= DEVICE_MASKS_MIN) {             // the party's own ChaCha12 stream, drawn on the device
-                    uint64_t after = 0;
-                    CG(cg_chacha12_fr_rand_dev(ctx, curve.id, (const uint8_t*)sh_gen.key, sh_gen.word_pos, len * (size_t)sh_t, d_all, &after));
-                    sh_gen.word_pos = after;
-                } else {
-                    std::vector<Fr> coeff(len * (size_t)sh_t);
-                    shamir_draw(coeff.size(), coeff.data());
-                    CG(cg_dev_upload(ctx, d_all, coeff.data(), coeff.size() * 32));
-                }
-            }
-            std::vector<void*> outs(np);
-            outs[0] = local.c[0];
-            for (int to = 1; to < np; to++) outs[to] = held.get(len * 32);
-            share_dev(local.c[0], d_all, 0, sh_t, len, sh_t, outs, 0, 1);
-            for (int to = np - 1; to >= 1; to--) { CG(cg_dev_download(ctx, buf, outs[to], len * 32)); snet->send(to, buf, len * 32); }
-            mk.mark("reshare+send");
-        } else {
-            if (me <= 2 * sh_t) { CG(cg_dev_download(ctx, buf, local.c[0], len * 32)); snet->send(0, buf, len * 32); }   // only if my items are required
-            mk.mark("download+send");
-            snet->recv(0, buf, len * 32);
-            mk.mark("wait for king");
-            CG(cg_dev_upload(ctx, local.c[0], buf, len * 32)); check_received_dev(local.c[0], len);
-            mk.mark("upload");
-        }
-        if (on_dev) {
-            lincomb(tmp, 0, 1, len, {{d_pre_rt, (int64_t)(top - 1 - pre_base), -1, one}});
-            sh_r_t.resize(top - len); sh_r_2t.resize(top - len);
-            pairs_consumed += len; pairs_from_device += len;
-        } else CG(cg_dev_upload(ctx, tmp, rt.data(), len * 32));
-        CG(cg_vec_sub_dev(ctx, curve.id, local.c[0], local.c[0], tmp, len));          // share - r_t
-        mk.mark("sub r_t");
-        return local;
-    }
-    Fr degree_reduce(Fr input) {                                                       // shamir.rs:252-300
-        const int np = snet->num_parties(), me = snet->id();
-        auto pr = get_pair();
-        input = fr_add(curve, input, pr.second);
-        Fr my_share;
-        if (me == 0) {
-            Fr acc = fr_mul(curve, input, mul_lagrange_2t[0]);
-            for (int other = 1; other <= 2 * sh_t; other++) { Fr r; snet->recv(other, r.v, 32); check_received(r.v, 1); acc = fr_add(curve, acc, fr_mul(curve, r, mul_lagrange_2t[other])); }
-            auto shares = shamir_share(acc, sh_t);
-            for (int to = 0; to < np; to++) { if (to == me) my_share = shares[to]; else snet->send(to, shares[to].v, 32); }
-        } else {
-            if (me <= 2 * sh_t) snet->send(0, input.v, 32);
-            snet->recv(0, my_share.v, 32); check_received(my_share.v, 1);
-        }
-        return fr_sub(curve, my_share, pr.first);
-    }
-    Point degree_reduce_point(Point input) {                                           // shamir.rs:386-436; C::rand stand-in: G * next_rand()
-        const int np = snet->num_parties(), me = snet->id();
-        const int g = input.group;
-        auto pr = get_pair();
-        const Point gen = pt_generator(curve, g);
-        input = pt_add(curve, input, pt_mul_generator(curve, g, pr.second));
-        Point my_share = pt_inf(curve, g);
-        const size_t psz = curve.aff(g);
-        if (me == 0) {
-            Point acc = pt_mul(curve, input, mul_lagrange_2t[0]);
-            for (int other = 1; other <= 2 * sh_t; other++) { Bytes a(psz); snet->recv(other, a.data(), psz); acc = pt_add(curve, acc, pt_mul(curve, received_point(g, a.data()), mul_lagrange_2t[other])); }
-            std::vector<Point> coeffs; for (int d = 0; d < sh_t; d++) coeffs.push_back(pt_mul_generator(curve, g, next_rand()));
-            for (int to = 0; to < np; to++) {
-                Point sh = acc; const Fr x = fr_from_u64(curve, (uint64_t)to + 1); Fr xp = x;
-                for (const Point& cf : coeffs) { sh = pt_add(curve, sh, pt_mul(curve, cf, xp)); xp = fr_mul(curve, xp, x); }
-                if (to == me) my_share = sh; else { Bytes a = pt_to_affine(curve, sh); snet->send(to, a.data(), a.size()); }
-            }
-        } else {
-            if (me <= 2 * sh_t) { Bytes a = pt_to_affine(curve, input); snet->send(0, a.data(), a.size()); }
-            Bytes a(psz); snet->recv(0, a.data(), psz); my_share = received_point(g, a.data());
-        }
-        return pt_sub(curve, my_share, pt_mul_generator(curve, g, pr.first));
-    }
-    // broadcast_next(t + 1) + reconstruct_point (network.rs:233-266, shamir.rs:778-782)
-    Point shamir_open_point(const Point& mine) {
-        const int np = snet->num_parties(), me = snet->id();
-        Bytes a = pt_to_affine(curve, mine);
-        for (int sft = 1; sft <= sh_t; sft++) snet->send((me + sft) % np, a.data(), a.size());
-        Point res = pt_mul(curve, mine, open_lagrange_t[0]);
-        for (int r = 1; r <= sh_t; r++) { Bytes b(a.size()); snet->recv((me + np - r) % np, b.data(), b.size()); res = pt_add(curve, res, pt_mul(curve, received_point(mine.group, b.data()), open_lagrange_t[r])); }
-        return res;
-    }
-
-    void* dalloc(size_t bytes) { void* p; CG(cg_dev_alloc(ctx, bytes, &p)); return p; }
+    // a randomness source that describes its ChaCha12 generators has its masks drawn by the backend (no host draws, no upload); short vectors
+    // are not worth three launches and a stream synchronisation — up to 2^10 elements: a host draw costs ~70 ns per element (two generators,
+    // rejection sampling), 0.6 ms per mul_vec at 2^13 (one REP3 party there: 2.75 ms with host draws, 2.14 with device draws; 2^11: 1.52 -> 1.40)
+    const size_t DEVICE_MASKS_MIN = (size_t)host_option(CGH_OPT_DEVICE_MASKS_MIN);   // (the override lets the small fixtures take the device path)
+};
+}  // namespace cgh
+#include "shamir.hpp"
+namespace cgh {
+class HipDriver : public DriverBase {
+public:
+    Mode mode; Rep3Network* net;
+    const Fr* rng1 = nullptr; const Fr* rng2 = nullptr; size_t rng_len = 0, cursor = 0;   // rngs.rs:25-46 streams (inputs)
+    // REP3 with the caller's own Rep3Rand (cgh_session_prove_rep3_party): every draw goes through it instead of the two arrays above
+    Rep3RandSource* rsrc = nullptr;
+    int k() const { return k_override ? k_override : (mode == Mode::Rep3 ? 2 : 1); }
+    // REP3 "additive quotient" variant (opt-in, NOT the reference's message sequence; see CoGroth16::prove): vector work on the own component only
+    int k_override = 0; bool additive_h = false;
+    struct Components { HipDriver& d; int old; Components(HipDriver& drv, int kk) : d(drv), old(drv.k_override) { d.k_override = kk; } ~Components() { d.k_override = old; } };
+    int party() const { return mode == Mode::Rep3 ? net->id() : -1; }
+    HipDriver(cg_ctx* c, Curve cv, Mode m, Rep3Network* n) : DriverBase(c, cv), mode(m), net(n) {}
+    // ---- Mode::Shamir: the party (shamir.hpp) behind the Shamir branches below; `source` is its private randomness
+    ShamirParty sh{*this};
+    void become_shamir_party(ShamirNet* n, int threshold, const ShamirRandom& source) { sh.init(n, threshold, source); }
     ShareVec alloc_vec(size_t n) { ShareVec v; v.n = n; for (int j = 0; j < k(); j++) { v.c[j] = dalloc(n * 32); CG(cg_dev_memset_zero(ctx, v.c[j], n * 32)); } return v; }
     void free_vec(ShareVec& v) { CG(cg_dev_free_many(ctx, v.c, 2)); v.c[0] = v.c[1] = nullptr; }
     // fence = false: the copies are started and this context's stream is NOT yet made to wait for them — the caller enqueues work that
@@ -479,7 +206,7 @@ public:
     // promote_to_trivial_shares (fieldshare.rs:262-283) + clone_from_slice (rep3.rs:710-725)
     // d_pub (optional): the same values already on the device — the copy is then enqueued like a kernel, the host does not wait
     void clone_public_into(ShareVec& dst, size_t dst_off, const std::vector<Fr>& pub, const void* d_pub = nullptr) {
-        const int holder = mode != Mode::Rep3 ? 0 : (party() == 0 ? 0 : party() == 1 ? 1 : -1);   // REP3: ID0 -> a, ID1 -> b, ID2 -> nothing; plain / Shamir: the value itself
+        const int holder = public_component();                                         // REP3: ID0 -> a, ID1 -> b, ID2 -> nothing; plain / Shamir: the value itself
         if (holder < 0) return;
         if (d_pub) CG(cg_dev_copy_peer(ctx, (uint8_t*)dst.c[holder] + dst_off * 32, ctx, d_pub, pub.size() * 32));
         else CG(cg_dev_upload(ctx, (uint8_t*)dst.c[holder] + dst_off * 32, pub.data(), pub.size() * 32));
@@ -542,10 +269,6 @@ public:
     // masks of the coming mul_vec calls, uploaded ahead of time (only from page-locked randomness streams, where the copy is a plain
     // asynchronous DMA): the product kernel then never waits for PCIe
     struct MaskSet { void* m1; void* m2; int32_t tk; size_t n, at; void* block = nullptr; bool owns = true; };   // block: m1 lies inside a block drawn for several calls; the LAST of them releases it
-    // a randomness source that describes its ChaCha12 generators has its masks drawn by the backend (no host draws, no upload); short vectors
-    // are not worth three launches and a stream synchronisation — up to 2^10 elements: a host draw costs ~70 ns per element (two generators,
-    // rejection sampling), 0.6 ms per mul_vec at 2^13 (one REP3 party there: 2.75 ms with host draws, 2.14 with device draws; 2^11: 1.52 -> 1.40)
-    const size_t DEVICE_MASKS_MIN = (size_t)host_option(CGH_OPT_DEVICE_MASKS_MIN);   // (the override lets the small fixtures take the device path)
     bool masks_on_device(void* d_m, size_t n) {
         if (!rsrc || n < DEVICE_MASKS_MIN) return false;
         void* tmp = nullptr;
@@ -623,7 +346,7 @@ public:
         if (mode != Mode::Rep3) CG(cg_vec_mul_dev(ctx, curve.id, out.c[0], a.c[0], b.c[0], a.n));
         if (mode == Mode::Plain) return pm;
         if (mode == Mode::Shamir) {                                                   // shamir.rs:609-623 (exchange = false: the degree-2t products)
-            if (exchange) { try { out = degree_reduce_vec(out); } catch (...) { cg_dev_free(ctx, out.c[0]); throw; } }
+            if (exchange) { try { out = sh.degree_reduce_vec(out); } catch (...) { cg_dev_free(ctx, out.c[0]); throw; } }
             return pm;
         }
         void* m1 = nullptr; void* m2 = nullptr; void* m1_block = nullptr; bool m1_owned = true;
@@ -639,22 +362,22 @@ public:
                 else { const int32_t tk = upload_staged(m1, rsrc->masking_field_elements(a.n, mask_scratch(a.n)), a.n); if (tk >= 0) CG(cg_copy_fence(ctx, tk)); }
             }
         } else {
-        if (cursor + a.n > rng_len) throw std::runtime_error("randomness stream exhausted");
-        if (!prefetched.empty() && prefetched.front().at == cursor && prefetched.front().n == a.n) {
-            const MaskSet ms = prefetched.front(); prefetched.pop_front();
-            m1 = ms.m1; m2 = ms.m2;
-            if (ms.tk >= 0) CG(cg_copy_fence(ctx, ms.tk));
-        } else {
-            m1 = dalloc(a.n * 32); m2 = dalloc(a.n * 32);
-        if (a.n < XCHG_ASYNC_MIN) { CG(cg_dev_upload(ctx, m1, rng1 + cursor, a.n * 32)); CG(cg_dev_upload(ctx, m2, rng2 + cursor, a.n * 32)); }
-        else {
-            upload_staged(m1, rng1 + cursor, a.n);
-            const int32_t tk = upload_staged(m2, rng2 + cursor, a.n);
-            if (tk >= 0) CG(cg_copy_fence(ctx, tk));                                   // uploads complete in order: the last ticket covers both masks
-        }
-        }
-        cursor += a.n;
-        CG(cg_vec_sub_dev(ctx, curve.id, m1, m1, m2, a.n));                           // masking_field_element = rand(rng1) - rand(rng2)
+            if (cursor + a.n > rng_len) throw std::runtime_error("randomness stream exhausted");
+            if (!prefetched.empty() && prefetched.front().at == cursor && prefetched.front().n == a.n) {
+                const MaskSet ms = prefetched.front(); prefetched.pop_front();
+                m1 = ms.m1; m2 = ms.m2;
+                if (ms.tk >= 0) CG(cg_copy_fence(ctx, ms.tk));
+            } else {
+                m1 = dalloc(a.n * 32); m2 = dalloc(a.n * 32);
+                if (a.n < XCHG_ASYNC_MIN) { CG(cg_dev_upload(ctx, m1, rng1 + cursor, a.n * 32)); CG(cg_dev_upload(ctx, m2, rng2 + cursor, a.n * 32)); }
+                else {
+                    upload_staged(m1, rng1 + cursor, a.n);
+                    const int32_t tk = upload_staged(m2, rng2 + cursor, a.n);
+                    if (tk >= 0) CG(cg_copy_fence(ctx, tk));                           // uploads complete in order: the last ticket covers both masks
+                }
+            }
+            cursor += a.n;
+            CG(cg_vec_sub_dev(ctx, curve.id, m1, m1, m2, a.n));                       // masking_field_element = rand(rng1) - rand(rng2)
         }
         CG(cg_vec_rep3_mul_local_dev(ctx, curve.id, out.c[0], a.c[0], a.c[1], b.c[0], b.c[1], m1, a.n));
         if (m1_owned) defer_free(m1_block ? m1_block : m1);                            // (a block drawn for several calls is released with the last of them)
@@ -748,8 +471,7 @@ public:
         if (!deferred.empty()) cg_dev_free_many(ctx, deferred.data(), deferred.size());
         deferred.clear();
         if (!mask_bufs.empty()) { cg_ctx_sync(ctx); for (void* p : mask_bufs) cg_host_free(p); mask_bufs.clear(); }   // uploads from them may still be in flight
-        release_rings(); release_pre();
-        if (sh_stage) { cg_host_free(sh_stage); sh_stage = nullptr; sh_stage_n = 0; }
+        release_rings(); sh.release();
         if (aux) { if (owns_aux) cg_ctx_destroy(aux); aux = nullptr; }
     }
     void sync_other_contexts() {                                                           // error paths: see VecGuard
@@ -760,30 +482,8 @@ public:
     ~HipDriver() { shutdown(); }
     // ---- vector forms of rand / mul_open_many / open_many used by co-plonk (rep3.rs:544-558,595-598,620-628,738-757)
     int public_component() const { return mode != Mode::Rep3 ? 0 : (party() == 0 ? 0 : party() == 1 ? 1 : -1); }   // add_with_public: who holds a public addend
-    // broadcast_next(num) of a vector + reconstruction with the given Lagrange table (shamir/network.rs:233-266, shamir.rs:581-601,684-711)
-    std::vector<Fr> shamir_open_vec(const std::vector<Fr>& mine, const std::vector<Fr>& lagrange) {
-        const int np = snet->num_parties(), me = snet->id(), num = (int)lagrange.size();
-        const size_t n = mine.size();
-        for (int sft = 1; sft < num; sft++) snet->send((me + sft) % np, mine.data(), n * 32);
-        std::vector<Fr> out(n), got(n);
-        for (size_t i = 0; i < n; i++) out[i] = fr_mul(curve, mine[i], lagrange[0]);
-        for (int r = 1; r < num; r++) { snet->recv((me + np - r) % np, got.data(), n * 32); check_received(got.data(), n); for (size_t i = 0; i < n; i++) out[i] = fr_add(curve, out[i], fr_mul(curve, got[i], lagrange[r])); }
-        return out;
-    }
     ShareVec rand_vec(size_t n) {
-        if (mode == Mode::Shamir) {                                                   // shamir.rs:570-573: the r_t halves of the n pairs on top of the LIFO, top first
-            const size_t top = sh_r_t.size();
-            if (n && !pre_on_host && top >= n && top - n >= pre_base && top <= pre_base + pre_n) {   // all in the device-resident block: one launch, no value crosses PCIe
-                ShareVec v; v.n = n; v.c[0] = dalloc(n * 32);
-                lincomb(v.c[0], 0, 1, n, {{d_pre_rt, (int64_t)(top - 1 - pre_base), -1, fr_from_u64(curve, 1)}});
-                sh_r_t.resize(top - n); sh_r_2t.resize(top - n);
-                pairs_consumed += n; pairs_from_device += n;
-                return v;
-            }
-            if (n > 1) materialize_pre();                                              // (one download of the block instead of two 32-byte copies per pair)
-            std::vector<Fr> r(n); for (size_t i = 0; i < n; i++) r[i] = get_pair().first;
-            return upload_vec(r.data(), nullptr, n);
-        }
+        if (mode == Mode::Shamir) { std::vector<Fr> r; ShareVec v = sh.rand_vec(n, r); return v.c[0] ? v : upload_vec(r.data(), nullptr, n); }   // shamir.rs:570-573
         if (mode != Mode::Rep3) throw std::runtime_error("rand_vec: REP3 / Shamir only");
         if (rsrc) { std::vector<Fr> a(n), b(n); for (size_t i = 0; i < n; i++) rsrc->random_fes(a[i], b[i]); return upload_vec(a.data(), b.data(), n); }
         if (cursor + n > rng_len) throw std::runtime_error("randomness stream exhausted");
@@ -796,29 +496,7 @@ public:
         void* out = dalloc(n * 32);
         if (mode != Mode::Rep3) CG(cg_vec_mul_dev(ctx, curve.id, out, a.c[0], b.c[0], n));
         if (mode == Mode::Plain) return out;
-        if (mode == Mode::Shamir) {                                                   // degree-2t product opened from 2t + 1 shares (shamir.rs:684-711)
-            // broadcast_next(2t) + reconstruction (shamir/network.rs:233-266): the Lagrange combination runs on the device
-            // messages staged in page-locked memory; from XCHG_STAGED_MIN elements on what arrives is range-checked on the device behind
-            // its upload (read before the next opening, verify_received_vectors), as mul_vec_finish does
-            const int np = snet->num_parties(), me = snet->id(), num = (int)open_lagrange_2t.size();
-            const bool staged = n >= XCHG_STAGED_MIN;
-            DevTmp got(*this);
-            try {
-                Fr* const buf = shamir_stage(n);
-                CG(cg_dev_download(ctx, buf, out, n * 32));
-                for (int sft = 1; sft < num; sft++) snet->send((me + sft) % np, buf, n * 32);
-                std::vector<Term> terms{{out, 0, 1, open_lagrange_2t[0]}};
-                for (int r = 1; r < num; r++) {
-                    snet->recv((me + np - r) % np, buf, n * 32);
-                    if (!staged) check_received(buf, n);
-                    void* d = got.get(n * 32); CG(cg_dev_upload(ctx, d, buf, n * 32));
-                    if (staged) check_received_dev(d, n);
-                    terms.push_back({d, 0, 1, open_lagrange_2t[r]});
-                }
-                lincomb(out, 0, 1, n, terms);
-            } catch (...) { cg_dev_free(ctx, out); throw; }
-            return out;
-        }
+        if (mode == Mode::Shamir) { try { sh.mul_open_vec(out, n, n >= XCHG_STAGED_MIN); } catch (...) { cg_dev_free(ctx, out); throw; } return out; }   // shamir.rs:684-711
         void* m1 = dalloc(n * 32); void* m2 = dalloc(n * 32);
         if (rsrc) { std::vector<Fr> buf(n); CG(cg_dev_upload(ctx, m1, rsrc->masking_field_elements(n, buf.data()), n * 32)); }
         else {
@@ -839,7 +517,7 @@ public:
     std::vector<Fr> open_many(const std::vector<FieldShare>& a) {
         std::vector<Fr> out(a.size());
         if (mode == Mode::Plain) { for (size_t i = 0; i < a.size(); i++) out[i] = a[i].c[0]; return out; }
-        if (mode == Mode::Shamir) { std::vector<Fr> mine(a.size()); for (size_t i = 0; i < a.size(); i++) mine[i] = a[i].c[0]; return shamir_open_vec(mine, open_lagrange_t); }   // shamir.rs:581-601
+        if (mode == Mode::Shamir) { std::vector<Fr> mine(a.size()); for (size_t i = 0; i < a.size(); i++) mine[i] = a[i].c[0]; return sh.open_vec(mine); }   // shamir.rs:581-601
         std::vector<Fr> bs(a.size()), cs(a.size());
         for (size_t i = 0; i < a.size(); i++) bs[i] = a[i].c[1];
         net->send_next(bs.data(), bs.size() * 32); net->recv_prev(cs.data(), cs.size() * 32); check_received(cs.data(), cs.size());
@@ -1030,7 +708,7 @@ public:
     }
     // rand (rep3.rs:595-598; plain: supplied by the caller)
     FieldShare rand() {
-        if (mode == Mode::Shamir) { FieldShare f; f.c[0] = get_pair().first; f.c[1] = f.c[0]; return f; }   // shamir.rs:570-573
+        if (mode == Mode::Shamir) { FieldShare f; f.c[0] = sh.get_pair().first; f.c[1] = f.c[0]; return f; }   // shamir.rs:570-573
         FieldShare f;
         if (rsrc) { rsrc->random_fes(f.c[0], f.c[1]); return f; }
         f.c[0] = draw(rng1); f.c[1] = draw(rng2); cursor++; return f;
@@ -1039,7 +717,7 @@ public:
     FieldShare mul(const FieldShare& a, const FieldShare& b) {
         FieldShare r;
         if (mode == Mode::Plain) { r.c[0] = fr_mul(curve, a.c[0], b.c[0]); r.c[1] = r.c[0]; return r; }
-        if (mode == Mode::Shamir) { r.c[0] = degree_reduce(fr_mul(curve, a.c[0], b.c[0])); r.c[1] = r.c[0]; return r; }   // shamir.rs:481-488
+        if (mode == Mode::Shamir) { r.c[0] = sh.degree_reduce(fr_mul(curve, a.c[0], b.c[0])); r.c[1] = r.c[0]; return r; }   // shamir.rs:481-488
         Fr local = fr_add(curve, fr_add(curve, fr_mul(curve, a.c[0], b.c[0]), fr_mul(curve, a.c[0], b.c[1])), fr_mul(curve, a.c[1], b.c[0]));
         if (rsrc) { Fr buf; local = fr_add(curve, local, *rsrc->masking_field_elements(1, &buf)); }
         else { local = fr_add(curve, local, fr_sub(curve, draw(rng1), draw(rng2))); cursor++; }
@@ -1061,7 +739,7 @@ public:
     PointShare scalar_mul(const PointShare& a, const FieldShare& b) {           // rep3.rs:835-847, pointshare.rs:117-124
         PointShare r;
         if (mode == Mode::Plain) { r.c[0] = pt_mul(curve, a.c[0], b.c[0]); r.c[1] = pt_inf(curve, a.c[0].group); return r; }
-        if (mode == Mode::Shamir) { r.c[0] = degree_reduce_point(pt_mul(curve, a.c[0], b.c[0])); r.c[1] = pt_inf(curve, a.c[0].group); return r; }   // shamir.rs:769-776
+        if (mode == Mode::Shamir) { r.c[0] = sh.degree_reduce_point(pt_mul(curve, a.c[0], b.c[0])); r.c[1] = pt_inf(curve, a.c[0].group); return r; }   // shamir.rs:769-776
         // three independent variable-base products (~60 us each in G1 on the host): two of them on helper threads (Helpers) — they sit between the
         // last MSM result and the proof, on every proof's tail
         auto p1 = Helpers::get().run([&] { return pt_mul(curve, a.c[1], b.c[0]); });
@@ -1088,7 +766,7 @@ public:
     }
     Point open_point(const PointShare& a) {                                      // rep3.rs:849-853
         if (mode == Mode::Plain) return a.c[0];
-        if (mode == Mode::Shamir) return shamir_open_point(a.c[0]);
+        if (mode == Mode::Shamir) return sh.open_point(a.c[0]);
         Bytes mine = pt_to_affine(curve, a.c[1]);
         net->send_next(mine.data(), mine.size());
         Bytes prev(mine.size()); net->recv_prev(prev.data(), prev.size());
@@ -1096,26 +774,7 @@ public:
     }
     std::pair<Point, Point> open_two_points(const PointShare& a, const PointShare& b) {   // rep3.rs:865-877
         if (mode == Mode::Plain) return {a.c[0], b.c[0]};
-        if (mode == Mode::Shamir) {   // shamir.rs:808-824 (one message per point here)
-            // both points are sent first, the G2 point's own term (a 254-bit product, as long as the whole G1 opening) runs on a helper under the G1
-            // opening; the messages keep their order on every channel (G1 then G2)
-            const int np = snet->num_parties(), me = snet->id();
-            const Bytes m1 = pt_to_affine(curve, a.c[0]), m2 = pt_to_affine(curve, b.c[0]);
-            for (int sft = 1; sft <= sh_t; sft++) { snet->send((me + sft) % np, m1.data(), m1.size()); snet->send((me + sft) % np, m2.data(), m2.size()); }
-            auto own2 = Helpers::get().run([&] { return pt_mul(curve, b.c[0], open_lagrange_t[0]); });
-            struct Joined { std::future<Point>& f; ~Joined() { if (f.valid()) f.wait(); } } joined{own2};     // (the helper reads this frame)
-            Point r1 = pt_mul(curve, a.c[0], open_lagrange_t[0]);
-            std::vector<Point> theirs2;
-            for (int r = 1; r <= sh_t; r++) {
-                Bytes b1(m1.size()), b2(m2.size());
-                snet->recv((me + np - r) % np, b1.data(), b1.size()); snet->recv((me + np - r) % np, b2.data(), b2.size());
-                theirs2.push_back(received_point(CG_G2, b2.data()));
-                r1 = pt_add(curve, r1, pt_mul(curve, received_point(CG_G1, b1.data()), open_lagrange_t[r]));
-            }
-            Point r2 = own2.get();
-            for (int r = 1; r <= sh_t; r++) r2 = pt_add(curve, r2, pt_mul(curve, theirs2[(size_t)r - 1], open_lagrange_t[r]));
-            return {r1, r2};
-        }
+        if (mode == Mode::Shamir) return sh.open_two_points(a.c[0], b.c[0]);          // shamir.rs:808-824
         Bytes m1 = pt_to_affine(curve, a.c[1]), m2 = pt_to_affine(curve, b.c[1]);
         Bytes msg(m1); msg.insert(msg.end(), m2.begin(), m2.end());
         net->send_next(msg.data(), msg.size());

@@ -201,7 +201,7 @@ public:
             for (int i : {AUX_A, AUX_B1, AUX_B2, AUX_L}) early[i] = driver.msm_finish(aux_msm, i);
             early[4] = driver.msm_finish(h_msm, 0);
             if (driver.mode == Mode::Rep3) driver.reshare_points({&early[0], &early[1], &early[2], &early[3], &early[4]});
-            else early[4].c[0] = driver.degree_reduce_point(early[4].c[0]);                            // Shamir: h was a degree-2t sharing
+            else early[4].c[0] = driver.sh.degree_reduce_point(early[4].c[0]);                         // Shamir: h was a degree-2t sharing
             have_early = true;
             mk.mark("msms + reshare (additive)");
         }
