@@ -106,6 +106,32 @@ def _dp(x):
     raise TypeError(f"not a device pointer: {type(x)}")
 
 
+def _fa(a):
+    """contiguous uint64 array of host-side field constants (or None)"""
+    return None if a is None else np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def _ptr_list(bufs):
+    """array of device pointers (or None); a None entry is NULL"""
+    if bufs is None:
+        return None
+    return (C.c_void_p * max(1, len(bufs)))(*[None if b is None else _dp(b).value for b in bufs])
+
+
+def _share_table(bufs, nv):
+    """pointer table [v * 2 + j] of nv vectors from the flat list of nv x k buffers [a0, (a1), b0, (b1), ..]: NULL second entries for k == 1"""
+    if bufs is None:
+        return None
+    per = len(bufs) // nv
+    assert per in (1, 2) and per * nv == len(bufs), f"{len(bufs)} buffers are not 1 or 2 components of {nv} vectors"
+    tab = (C.c_void_p * (2 * nv))()
+    for v in range(nv):
+        for j in range(per):
+            b = bufs[v * per + j]
+            tab[2 * v + j] = None if b is None else _dp(b).value
+    return tab
+
+
 def fq_limbs(curve):
     return 6 if curve == BLS12_381 else 4
 
@@ -433,12 +459,46 @@ class Context:
         _chk(load().cg_shamir_share_dev(self.h, curve, _dp(secrets), _dp(coeffs), C.c_int64(coeff_off), C.c_int64(coeff_stride), C.c_size_t(n), int(degree),
                                         len(outs), ptrs, C.c_int64(out_off), C.c_int64(out_stride)))
 
+    # ---- co-plonk's fused kernels (csrc/plonk_kernels.hpp).  A share table is a flat list of nv x k buffers [a0, (a1), b0, (b1), ..]; it
+    # becomes the ABI's pointer table [v * 2 + j] with NULL second entries for k == 1.  None (a table, an entry, a constant) is passed as NULL.
+    def plonk_additions(self, curve, order, n, ids, coeffs, pub, n_inputs, public_component, ext_a, ext_b, n_priv, order_off=0):
+        """one dependency level of round 1's additions (cg_plonk_additions_dev): the n additions order[order_off ..] of the list (ids, coeffs),
+        written to ext[n_priv + a] of every component; ext_b = None for one share component"""
+        po = None if order is None else C.c_void_p(_dp(order).value + 4 * int(order_off))
+        _chk(load().cg_plonk_additions_dev(self.h, curve, po, C.c_size_t(n), _dp(ids), _dp(coeffs), _dp(pub), C.c_uint32(n_inputs), int(public_component),
+                                           _dp(ext_a), _dp(ext_b), C.c_size_t(n_priv)))
+
     def plonk_r2_factors(self, curve, k, public_component, n, pw, pw_stride, sigmas, sigma_stride, coeffs, wires, outs):
         """round 2's six factors (cg_plonk_r2_factors_dev): wires = 3 x k buffers [a0, a1, b0, ..], outs = 6 x k likewise; coeffs = beta, beta k1, beta k2, gamma"""
-        tab = lambda lst: (C.c_void_p * (2 * (len(lst) // k)))(*[v for i in range(len(lst) // k) for v in ([_dp(lst[i * k + j]).value for j in range(k)] + [None] * (2 - k))])
-        sg = (C.c_void_p * 3)(*[_dp(x).value for x in sigmas])
-        _chk(load().cg_plonk_r2_factors_dev(self.h, curve, int(k), int(public_component), C.c_size_t(n), _dp(pw), C.c_size_t(pw_stride), sg, C.c_size_t(sigma_stride),
-                                            _hp(np.ascontiguousarray(coeffs, dtype=np.uint64)), tab(wires), tab(outs)))
+        _chk(load().cg_plonk_r2_factors_dev(self.h, curve, int(k), int(public_component), C.c_size_t(n), _dp(pw), C.c_size_t(pw_stride), _ptr_list(sigmas), C.c_size_t(sigma_stride),
+                                            _hp(_fa(coeffs)), _share_table(wires, 3), _share_table(outs, 6)))
+
+    def plonk_r3_blind(self, curve, k, n, pw, omega, blind, outs):
+        """round 3's blinding polynomials on pw (cg_plonk_r3_blind_dev): blind = k x 9 coefficients b_1..b_9 per component, outs = 5 x k buffers ap, bp, cp, zp, zwp"""
+        _chk(load().cg_plonk_r3_blind_dev(self.h, curve, int(k), C.c_size_t(n), _dp(pw), _hp(_fa(omega)), _hp(_fa(blind)), _share_table(outs, 5)))
+
+    def plonk_r3_perm(self, curve, k, public_component, n, pw, sigmas, coeffs, wires, outs):
+        """round 3's six permutation factors (cg_plonk_r3_perm_dev): the arguments of plonk_r2_factors without the strides"""
+        _chk(load().cg_plonk_r3_perm_dev(self.h, curve, int(k), int(public_component), C.c_size_t(n), _dp(pw), _ptr_list(sigmas), _hp(_fa(coeffs)),
+                                         _share_table(wires, 3), _share_table(outs, 6)))
+
+    def plonk_r3_gate(self, curve, k, public_component, n, q, lagrange, n_lagrange, ins, z1, outs):
+        """the gate constraint and its blinding twin (cg_plonk_r3_gate_dev): q = qm, ql, qr, qo, qc; lagrange = n_lagrange rows of n; ins = 11 x k buffers
+        buffer_a, a b, a b', a' b, a' b', a, b, c, a', b', c'; z1 = 4 constants; outs = 2 x k buffers e1, e1z"""
+        _chk(load().cg_plonk_r3_gate_dev(self.h, curve, int(k), int(public_component), C.c_size_t(n), _ptr_list(q), _dp(lagrange), C.c_size_t(n_lagrange),
+                                         _share_table(ins, 11), _hp(_fa(z1)), _share_table(outs, 2)))
+
+    def plonk_mul4_tail(self, curve, k, n, prods, z, rz):
+        """the linear end of mul4vec_post (cg_plonk_mul4_tail_dev): prods = 8 x k buffers, z = 3 x 4 constants Z1, Z2, Z3, rz = k buffers"""
+        _chk(load().cg_plonk_mul4_tail_dev(self.h, curve, int(k), C.c_size_t(n), _share_table(prods, 8), _hp(_fa(z)), _share_table(rz, 1)))
+
+    def plonk_r3_t(self, curve, k, public_component, n, l1, ins, alpha, outs):
+        """t and tz before the inverse NTTs (cg_plonk_r3_t_dev): ins = 8 x k buffers e1, e1z, e2, e3, e2z, e3z, z, z'; outs = 2 x k buffers t, tz"""
+        _chk(load().cg_plonk_r3_t_dev(self.h, curve, int(k), int(public_component), C.c_size_t(n), _dp(l1), _share_table(ins, 8), _hp(_fa(alpha)), _share_table(outs, 2)))
+
+    def plonk_r3_divide(self, curve, k, n, t, tz):
+        """the division by X^n - 1 and + tz, in place on t (cg_plonk_r3_divide_dev): t, tz = k buffers of 4n elements"""
+        _chk(load().cg_plonk_r3_divide_dev(self.h, curve, int(k), C.c_size_t(n), _share_table(t, 1), _share_table(tz, 1)))
 
     def vec_prefix_prod(self, curve, out, src, n): _chk(load().cg_vec_prefix_prod_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
     def vec_prefix_sum(self, curve, out, src, n): _chk(load().cg_vec_prefix_sum_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
