@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "cg_plonk_additions_dev", "cg_plonk_r2_factors_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
+    "cg_pairing", "cg_final_exp", "cg_fp12_mul", "cg_fp12_pow", "cg_miller_loop", "cg_pairing_check", "cg_miller_batch", "cg_miller_product", "cg_final_exp_check_batch",
     "cg_bases_synth_multiples", "cg_bases_download", "cg_bases_from_scalars",
     "cg_dev_copy_peer", "cg_ctx_device", "cg_device_count", "cg_device_preflight",
     "cg_stats_enable", "cg_stats",
@@ -307,6 +308,32 @@ class Context:
 
     def copy_wait(self, ticket): _chk(load().cg_copy_wait(self.h, int(ticket)))
     def copy_fence(self, ticket): _chk(load().cg_copy_fence(self.h, int(ticket)))
+
+    # ---- pairing batches (cg_miller_batch / cg_miller_product / cg_final_exp_check_batch): one lane per (P, Q) pair
+    def miller_batch(self, curve, g1, g2):
+        """the n Miller values of packed affine pairs (g1[i], g2[i]) as (n, 2, 3, 2, limbs); cg.final_exp of one is the pairing"""
+        g1, g2 = _pairs(curve, g1, g2)
+        out = np.zeros((g1.shape[0], 2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+        _chk(load().cg_miller_batch(self.h, curve, _hp(g1), _hp(g2), C.c_size_t(g1.shape[0]), _hp(out)))
+        return out
+
+    def miller_product(self, curve, g1, g2, scalars128=None):
+        """product of the Miller values of (k_i g1[i], g2[i]), no final exponentiation; scalars128: (n, 2) u64 canonical 128-bit integers k_i"""
+        g1, g2 = _pairs(curve, g1, g2)
+        k = None if scalars128 is None else np.ascontiguousarray(scalars128, dtype=np.uint64).reshape(g1.shape[0], 2)
+        out = np.zeros((2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+        _chk(load().cg_miller_product(self.h, curve, _hp(g1), _hp(g2), _hp(k), C.c_size_t(g1.shape[0]), _hp(out)))
+        return out
+
+    def final_exp_check_batch(self, curve, values, k, target):
+        """flags[i] = FE(values[i k] * .. * values[i k + k - 1]) == target for n groups of k Miller values"""
+        nq = fq_limbs(curve)
+        v = np.ascontiguousarray(values, dtype=np.uint64).reshape(-1, 12 * nq)
+        n = v.shape[0] // int(k)
+        assert n * int(k) == v.shape[0]
+        ok = np.zeros(n, dtype=np.int32)
+        _chk(load().cg_final_exp_check_batch(self.h, curve, _hp(v), int(k), C.c_size_t(n), _hp(np.ascontiguousarray(target, dtype=np.uint64)), _hp(ok)))
+        return ok.astype(bool)
 
     # ---- MSM
     def register_bases(self, curve, group, points, stride=None, infinity_offset=-1):
@@ -657,6 +684,64 @@ def fr_op(curve, op, a, b=None):
     return out
 
 
+# ---- pairing on the host (cg_pairing ...): target-field elements are (2, 3, 2, limbs) u64, Montgomery, the layout of vk_alphabeta_12
+def _pairs(curve, g1, g2):
+    nq = fq_limbs(curve)
+    g1 = np.ascontiguousarray(g1, dtype=np.uint64).reshape(-1, 2 * nq); g2 = np.ascontiguousarray(g2, dtype=np.uint64).reshape(-1, 4 * nq)
+    assert g1.shape[0] == g2.shape[0], "as many G1 as G2 points"
+    return g1, g2
+
+
+def pairing(curve, g1_affine, g2_affine):
+    """e(P, Q) with arkworks' / snarkjs' value convention; host arithmetic, no device"""
+    g1, g2 = _pairs(curve, g1_affine, g2_affine)
+    out = np.zeros((2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+    _chk(load().cg_pairing(curve, _hp(g1), _hp(g2), _hp(out)))
+    return out
+
+
+def final_exp(curve, value):
+    out = np.zeros((2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+    _chk(load().cg_final_exp(curve, _hp(np.ascontiguousarray(value, dtype=np.uint64)), _hp(out)))
+    return out
+
+
+def fp12_mul(curve, a, b):
+    out = np.zeros((2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+    _chk(load().cg_fp12_mul(curve, _hp(np.ascontiguousarray(a, dtype=np.uint64)), _hp(np.ascontiguousarray(b, dtype=np.uint64)), _hp(out)))
+    return out
+
+
+def fp12_pow(curve, a, exponent):
+    """a^exponent for a non-negative Python integer"""
+    nl = max(1, (int(exponent).bit_length() + 63) // 64)
+    e = np.array([(int(exponent) >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(nl)], dtype=np.uint64)
+    out = np.zeros((2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+    _chk(load().cg_fp12_pow(curve, _hp(np.ascontiguousarray(a, dtype=np.uint64)), _hp(e), nl, _hp(out)))
+    return out
+
+
+def fp12_one(curve):
+    """the target field's one: the Miller value of no pairs"""
+    return miller_loop(curve, np.zeros((0, 2 * fq_limbs(curve)), dtype=np.uint64), np.zeros((0, 4 * fq_limbs(curve)), dtype=np.uint64))
+
+
+def miller_loop(curve, g1, g2):
+    """product of the Miller values of the pairs, no final exponentiation; host arithmetic"""
+    g1, g2 = _pairs(curve, g1, g2)
+    out = np.zeros((2, 3, 2, fq_limbs(curve)), dtype=np.uint64)
+    _chk(load().cg_miller_loop(curve, _hp(g1), _hp(g2), C.c_size_t(g1.shape[0]), _hp(out)))
+    return out
+
+
+def pairing_check(curve, g1, g2):
+    """prod e(g1[i], g2[i]) == 1 with one final exponentiation; host arithmetic"""
+    g1, g2 = _pairs(curve, g1, g2)
+    ok = C.c_int32(0)
+    _chk(load().cg_pairing_check(curve, _hp(g1), _hp(g2), C.c_size_t(g1.shape[0]), C.byref(ok)))
+    return bool(ok.value)
+
+
 # ---- host-side mirror of the reference prover interface (libcogroth16_host.so, C++ over the C ABI) -----------------------
 _host = None
 
@@ -804,6 +889,15 @@ class ProvingSession:
                                                   _hp(np.ascontiguousarray(s, dtype=np.uint64)), _hp(out), sec))
         return out, sec[0]
 
+    def verify(self, proof, pub):
+        """Groth16::verify of a proof against the session's own key (cgh_session_verify); pub = the n_public public inputs, Montgomery"""
+        ok = C.c_int32(0)
+        pub = np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 4)
+        if pub.shape[0] != self.info["n_public"]:
+            raise BackendError(f"cogroth16_host: {pub.shape[0]} public inputs for a key with {self.info['n_public']}")
+        _hchk(load_host().cgh_session_verify(self.h, _hp(np.ascontiguousarray(proof, dtype=np.uint64)), _hp(pub), C.byref(ok)))
+        return bool(ok.value)
+
     def prove_rep3(self, pub, wit_a, wit_b, streams, solo=True):
         """three co-located parties; returns (3 proofs, seconds of the three together, seconds of party 0 replayed alone on the GPU)"""
         nq = 6 if self.curve == BLS12_381 else 4
@@ -813,6 +907,65 @@ class ProvingSession:
         _hchk(load_host().cgh_session_prove_rep3(self.h, _hp(np.ascontiguousarray(pub, dtype=np.uint64)), arr(keep[0]), arr(keep[1]), arr(keep[2]),
                                                  C.c_size_t(keep[2][0].shape[0]), _hp(out), sec if solo else None))
         return out, sec[0], sec[1]
+
+
+class VerifyingKey:
+    """Groth16 verifying key (cgh_vk_*): points validated, e(alpha, beta), -gamma and -delta prepared when the handle is opened"""
+
+    def __init__(self, curve, handle):
+        self.curve, self.h = curve, handle
+        info = (C.c_size_t * 2)()
+        _hchk(load_host().cgh_vk_info(self.h, info))
+        self.n_public = int(info[1])
+
+    @classmethod
+    def from_json(cls, curve, path):
+        h = C.c_void_p()
+        _hchk(load_host().cgh_vk_from_json(curve, path.encode(), C.byref(h)))
+        return cls(curve, h)
+
+    @classmethod
+    def from_zkey(cls, curve, path):
+        h = C.c_void_p()
+        _hchk(load_host().cgh_vk_from_zkey(curve, path.encode(), C.byref(h)))
+        return cls(curve, h)
+
+    def close(self):
+        if self.h: load_host().cgh_vk_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def alphabeta(self):
+        """the prepared e(alpha_1, beta_2) as (2, 3, 2, limbs): the layout of vk_alphabeta_12"""
+        out = np.zeros((2, 3, 2, fq_limbs(self.curve)), dtype=np.uint64)
+        _hchk(load_host().cgh_vk_alphabeta(self.h, _hp(out)))
+        return out
+
+    def verify(self, proof, pub):
+        """one proof on the host (cgh_groth16_verify); a wrong number of public inputs or a non-canonical one raises BackendError"""
+        pub = np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 4)
+        ok = C.c_int32(0)
+        _hchk(load_host().cgh_groth16_verify(self.h, _hp(np.ascontiguousarray(proof, dtype=np.uint64)), _hp(pub), C.c_size_t(pub.shape[0]), C.byref(ok)))
+        return bool(ok.value)
+
+    def verify_batch(self, proofs, pubs, seed=None, per_proof=False, device=0, timing=False):
+        """n proofs on the GPU with random 128-bit coefficients (cgh_groth16_verify_batch).  proofs: (n, proof words); pubs: (n, n_public, 4).
+        Returns the verdict; with per_proof=True (verdict, flags); with timing=True the five stage times in seconds are appended."""
+        nq = fq_limbs(self.curve)
+        proofs = np.ascontiguousarray(proofs, dtype=np.uint64).reshape(-1, 8 * nq)
+        n = proofs.shape[0]
+        pubs = np.ascontiguousarray(pubs, dtype=np.uint64).reshape(n, self.n_public, 4) if n else np.zeros((0, self.n_public, 4), dtype=np.uint64)
+        ok = C.c_int32(0)
+        flags = np.zeros(max(n, 1), dtype=np.uint8) if per_proof else None
+        secs = (C.c_double * 5)()
+        _hchk(load_host().cgh_groth16_verify_batch_timed(int(device), self.h, _hp(proofs), _hp(pubs), C.c_size_t(pubs.shape[1]), C.c_size_t(n),
+                                                         None if seed is None else bytes(seed), C.byref(ok), _hp(flags), secs))
+        out = (bool(ok.value),) + ((flags[:n].astype(bool),) if per_proof else ()) + ((list(secs),) if timing else ())
+        return out[0] if len(out) == 1 else out
 
 
 # ---- one REP3 party with the caller's network and randomness (cgh_session_prove_rep3_party) ------------------------------------

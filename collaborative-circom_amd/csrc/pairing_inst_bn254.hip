@@ -1,0 +1,3 @@
+// pairing kernels (Miller loop, Fp12 product tree, final exponentiation with comparison) for bn254 (explicit instantiation; see pairing_impl.hpp)
+#include "pairing_impl.hpp"
+CG_INSTANTIATE_PAIRING(Bn254Pairing)

@@ -2,6 +2,7 @@
 #include "groth16.hpp"
 #include "capi_common.hpp"
 #include "chacha.hpp"
+#include "verify.hpp"
 
 #include <map>
 extern "C" {
@@ -20,6 +21,7 @@ struct cgh_session {
     bool bulk_second = false;                                                            // the non-chain contexts run next to a chain context
     bool additive_h = false;                                                             // open flag bit 1: REP3 additive-quotient variant
     bool counted = false;                                                                // the session was opened successfully (it counts as open until closed)
+    std::unique_ptr<cgh::VerifyingKey> vk;                                               // cgh_session_verify: prepared from the zkey's header and IC at first use (under mu)
     cgh::SessionFixed fixed;                                                             // window tables of delta_1, delta_2 and the public-input records (host)
     // A free context is handed out in order of CREATION (lowest serial first), not of return: the pair made at session open serves a party
     // that proves alone in EVERY proof.  Contexts differ in how their streams fell onto the hardware queues; a first-returned-first-out
@@ -202,6 +204,15 @@ int32_t cgh_session_open(int32_t device, int32_t curve, const char* zkey_path, i
     return cgh_session_open_ex(device, curve, zkey_path, precompute, 0, out);
 }
 int32_t cgh_session_close(void* h) { session_destroy((cgh_session*)h); return 0; }
+// Groth16::verify (verifier.rs:23-43) with the key taken from the session's zkey: what a party runs on the proof it has just opened.  Host only.
+int32_t cgh_session_verify(void* h, const uint64_t* proof, const uint64_t* pub, int32_t* ok) {
+    try {
+        cgh_session* s = (cgh_session*)h;
+        if (!s || !proof || !ok || (s->z.n_public && !pub)) throw std::runtime_error("cgh_session_verify: null argument");
+        { std::lock_guard<std::mutex> l(s->mu); if (!s->vk) s->vk.reset(new cgh::VerifyingKey(cgh::vk_from_zkey_data(s->z))); }
+        *ok = cgh::groth16_verify(*s->vk, (const uint8_t*)proof, pub, s->z.n_public) ? 1 : 0; return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
 // plain driver on an open session; seconds[0] (optional) = wall time of the prove
 int32_t cgh_session_prove_plain(void* h, const uint64_t* full_witness, const uint64_t* r, const uint64_t* sc, uint64_t* out_proof, double* seconds) {
     cgh_session* s = (cgh_session*)h;

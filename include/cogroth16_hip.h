@@ -396,6 +396,34 @@ int32_t cg_fq_from_canonical(int32_t curve, const void* h_in, void* h_out, size_
 /* generator of G1/G2 as a Jacobian point (ark-bn254 / ark-bls12-381 constants) */
 int32_t cg_point_generator(int32_t curve, int32_t group, void* h_out);
 
+/* ---- pairing (ark-ec `Pairing::pairing` / `multi_miller_loop` / `final_exponentiation`, what ark-groth16's verify_proof behind
+ * co-groth16/src/verifier.rs:23-43 computes; csrc/pairing.hpp) --------------------------------------------------------------------
+ * A target-field element is 12 base-field elements, Montgomery, laid out (2, 3, 2, limbs): [i][j][k] = coefficient c_i.c_j.c_k of
+ * Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - xi) — the nesting of `vk_alphabeta_12` in a verification_key.json (384 B BN254, 576 B
+ * BLS12-381).  The VALUE is the optimal-ate pairing as arkworks 0.4 and snarkjs define it: e(alpha, beta) equals vk_alphabeta_12 limb for
+ * limb.  Points are packed affine, (0, 0) = infinity; an input at infinity in either group gives 1.  G2 inputs must lie in the prime-order
+ * subgroup (cg_point_validate / cg_bases_check_subgroup): for other points the value is meaningless (never a fault).
+ * A Miller value is the convention's loop output (conjugated for BLS12-381, whose parameter is negative): Miller values multiply, and
+ * the final exponentiation of a product is the product of the pairings.
+ *   pairing:        out = e(P, Q).                                                   host arithmetic, no device, no context
+ *   final_exp:      out = in^(c (p^12 - 1)/r), c = the convention's factor.         host
+ *   fp12_mul / pow: out = a b ; out = a^e, e = exp_limbs64 little-endian 64-bit words.   host (the verifier's O(1) tail)
+ *   miller_loop:    out = Miller(P_0, Q_0) * .. * Miller(P_(n-1), Q_(n-1)), no final exponentiation; n == 0 gives 1.   host
+ *   pairing_check:  *ok = (e(P_0, Q_0) * .. * e(P_(n-1), Q_(n-1)) == 1), one final exponentiation; n == 0 gives 1.   host
+ *   miller_batch:   out[i] = Miller(P_i, Q_i), i < n: one GPU lane per pair.
+ *   miller_product: out = product of Miller(k_i P_i, Q_i), i < n, no final exponentiation; h_scalars128 (optional) = n canonical
+ *                   little-endian 128-bit integers k_i (16 B each) applied to P_i on the device; NULL = all one.  n == 0 gives 1.
+ *   final_exp_check_batch: ok[i] = (FE(in[i k] * .. * in[i k + k - 1]) == target), i < n: one GPU lane per group of k Miller values. */
+int32_t cg_pairing(int32_t curve, const void* h_g1_affine, const void* h_g2_affine, void* h_out_fp12);
+int32_t cg_final_exp(int32_t curve, const void* h_in, void* h_out);
+int32_t cg_fp12_mul(int32_t curve, const void* h_a, const void* h_b, void* h_out);
+int32_t cg_fp12_pow(int32_t curve, const void* h_a, const void* h_exp, int32_t exp_limbs64, void* h_out);
+int32_t cg_miller_loop(int32_t curve, const void* h_g1, const void* h_g2, size_t n, void* h_out_fp12);
+int32_t cg_pairing_check(int32_t curve, const void* h_g1, const void* h_g2, size_t n, int32_t* ok);
+int32_t cg_miller_batch(cg_ctx* ctx, int32_t curve, const void* h_g1, const void* h_g2, size_t n, void* h_out_fp12s);
+int32_t cg_miller_product(cg_ctx* ctx, int32_t curve, const void* h_g1, const void* h_g2, const void* h_scalars128, size_t n, void* h_out_fp12);
+int32_t cg_final_exp_check_batch(cg_ctx* ctx, int32_t curve, const void* h_fp12s, int32_t k, size_t n, const void* h_target_fp12, int32_t* ok);
+
 /* ---- tooling (bench / tests; not on the prover path) ----------------------------------------------------------- */
 /* Builds, on the device, the table [(first + i) * G]_{i<n} of consecutive multiples of the group generator: valid,
  * pairwise distinct points with known discrete logs, used as synthetic zkey-sized bases. */

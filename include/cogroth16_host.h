@@ -127,6 +127,40 @@ int32_t cgh_session_prove_plain(void* session, const uint64_t* full_witness, con
 int32_t cgh_session_prove_rep3(void* session, const uint64_t* pub_in, const uint64_t* const* wit_a, const uint64_t* const* wit_b,
                                const uint64_t* const* streams, size_t stream_len, uint64_t* out_proofs, double* seconds);
 
+/* Groth16::verify with the verifying key taken from the session's zkey (alpha_1, beta_2, gamma_2, delta_2, IC; prepared at first use): what a
+ * party runs on the proof it has just opened.  pub = the n_public public inputs (without the leading one), Montgomery.  Host arithmetic. */
+int32_t cgh_session_verify(void* session, const uint64_t* proof, const uint64_t* pub, int32_t* ok);
+
+/* ---- Groth16 verification (co-groth16/src/verifier.rs:23-43: ark-groth16's prepare_verifying_key + verify_proof) ----------------------
+ * A verifying-key handle holds alpha_1, beta_2, gamma_2, delta_2 and IC from a verification_key.json (the fields
+ * circom-types/src/groth16/verification_key.rs reads) or from a zkey's header and IC section.  Opening one validates every point
+ * (cg_point_validate: on the curve, in the subgroup) and prepares e(alpha_1, beta_2) — COMPUTED, not read from `vk_alphabeta_12` — with
+ * -gamma_2 and -delta_2.  info[2]: curve, n_public.  alphabeta: the prepared e(alpha_1, beta_2), 12 base-field elements (2, 3, 2, limbs).
+ * A handle is immutable and may be used from several threads. */
+int32_t cgh_vk_from_json(int32_t curve, const char* path, void** out_vk);
+int32_t cgh_vk_from_zkey(int32_t curve, const char* path, void** out_vk);
+int32_t cgh_vk_info(void* vk, size_t* info);
+int32_t cgh_vk_alphabeta(void* vk, uint64_t* out_fp12);
+int32_t cgh_vk_free(void* vk);
+/* One proof, on the host (no device): *ok = 1 iff e(A, B) e(vk_x, -gamma) e(C, -delta) == e(alpha, beta), vk_x = IC_0 + sum pub_i IC_(i+1) —
+ * the check of ark-groth16's verify_proof.  proof = packed affine A || B || C, Montgomery, as the prove entries return it; pub = n_pub
+ * Montgomery scalars.  n_pub != |IC| - 1, or a public input not below the modulus, is an ERROR status, not a verdict.  A proof point off
+ * the curve or outside the subgroup gives *ok = 0 (the reference's proof parser rejects it). */
+int32_t cgh_groth16_verify(void* vk, const uint64_t* proof, const uint64_t* pub, size_t n_pub, int32_t* ok);
+/* n_proofs proofs under one key on the GPU `device` (proofs back to back, pubs = n_proofs x n_pub): with r_0 = 1 and r_1.. 128-bit
+ * coefficients from ChaCha12 (seed32, or OS entropy when NULL), *ok = 1 iff
+ *   FE( prod_i Miller(r_i A_i, B_i) * Miller(sum_i r_i vk_x_i, -gamma) * Miller(sum_i r_i C_i, -delta) ) == e(alpha, beta)^(sum_i r_i)
+ * after the on-curve and subgroup passes over the A, B, C arrays (cg_bases_check_on_curve / _subgroup); the Miller product is
+ * cg_miller_product, the two sums are cg_msm calls (the second over IC with the scalars sum r_i, sum r_i pub_i1, ..).  A batch with an
+ * invalid proof is accepted with probability at most 2^-128 over the coefficients.  When the batch is rejected and per_proof is given,
+ * every proof is decided on its own on the GPU (three Miller loops and a final exponentiation per lane) and per_proof[i] = 1 / 0; an
+ * accepted batch sets every flag.  n_proofs == 0 accepts.  Errors as for cgh_groth16_verify.
+ * _timed: seconds[5] (optional) = point checks, Miller kernel + product, MSM of the C points, scalar sums + MSM over IC, host tail. */
+int32_t cgh_groth16_verify_batch(int32_t device, void* vk, const uint64_t* proofs, const uint64_t* pubs, size_t n_pub, size_t n_proofs, const uint8_t* seed32,
+                                 int32_t* ok, uint8_t* per_proof);
+int32_t cgh_groth16_verify_batch_timed(int32_t device, void* vk, const uint64_t* proofs, const uint64_t* pubs, size_t n_pub, size_t n_proofs, const uint8_t* seed32,
+                                       int32_t* ok, uint8_t* per_proof, double* seconds);
+
 /* ---- ONE party of a REP3 proof, with the caller's network and the caller's correlated randomness ------------------------------------
  * This is what `co-circom generate-proof --protocol REP3` runs per process (co-circom.rs:484-506): the party's own shares, a network
  * to its two peers (Rep3MpcNet, mpc-core/src/protocols/rep3/network.rs:13-64) and the randomness it agreed on with them
