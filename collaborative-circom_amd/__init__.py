@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
     "cg_pairing", "cg_final_exp", "cg_fp12_mul", "cg_fp12_pow", "cg_miller_loop", "cg_pairing_check", "cg_miller_batch", "cg_miller_product", "cg_final_exp_check_batch",
+    "cg_plonk_verify_scalars", "cg_plonk_verify_scalars_host", "cg_g1_lincomb_batch",
     "cg_bases_synth_multiples", "cg_bases_download", "cg_bases_from_scalars",
     "cg_dev_copy_peer", "cg_ctx_device", "cg_device_count", "cg_device_preflight",
     "cg_stats_enable", "cg_stats",
@@ -336,6 +337,19 @@ class Context:
         return ok.astype(bool)
 
     # ---- MSM
+    def plonk_verify_scalars(self, curve, key, commits, evals, pubs, coeff128=None):
+        """cg_plonk_verify_scalars: one GPU lane per proof; see plonk_verify_scalars_host for the arguments and the result"""
+        return _plonk_verify_scalars(self.h, curve, key, commits, evals, pubs, coeff128)
+
+    def g1_lincomb_batch(self, curve, points, scalars):
+        """out[g] = sum_k scalars[g, k] points[g, k]: points (groups, K, point words) packed affine G1, scalars (groups, K, 4) Montgomery"""
+        nq = fq_limbs(curve)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64); groups, k = scalars.shape[0], scalars.shape[1]
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(groups, k, 2 * nq)
+        out = np.zeros((groups, 2 * nq), dtype=np.uint64)
+        _chk(load().cg_g1_lincomb_batch(self.h, curve, _hp(points), _hp(scalars), C.c_size_t(groups), int(k), _hp(out)))
+        return out
+
     def register_bases(self, curve, group, points, stride=None, infinity_offset=-1):
         pts = np.ascontiguousarray(points)
         rec = point_words(curve, group, 2) * 8
@@ -740,6 +754,36 @@ def pairing_check(curve, g1, g2):
     ok = C.c_int32(0)
     _chk(load().cg_pairing_check(curve, _hp(g1), _hp(g2), C.c_size_t(g1.shape[0]), C.byref(ok)))
     return bool(ok.value)
+
+
+# ---- Plonk verification, the per-proof layer (cg_plonk_verify_scalars{,_host}; csrc/plonk_verify.hpp) -----------------------------------
+def _plonk_verify_scalars(ctx_handle, curve, key, commits, evals, pubs, coeff128):
+    nq = fq_limbs(curve)
+    commits = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 9, 2 * nq)
+    n = commits.shape[0]
+    evals = np.ascontiguousarray(evals, dtype=np.uint64).reshape(n, 6, 4)
+    pubs = np.ascontiguousarray(pubs, dtype=np.uint64).reshape(n, -1, 4) if np.size(pubs) else np.zeros((n, 0, 4), dtype=np.uint64)
+    n_pub = pubs.shape[1]
+    if coeff128 is not None:
+        coeff128 = np.ascontiguousarray(coeff128, dtype=np.uint64).reshape(n, 2)
+    pts = np.ascontiguousarray(key["points"], dtype=np.uint64).reshape(8, 2 * nq)
+    ch = np.zeros((n, 6, 4), dtype=np.uint64); sp = np.zeros((n, 11, 4), dtype=np.uint64); sk = np.zeros((n, 9, 4), dtype=np.uint64)
+    valid = np.zeros(max(n, 1), dtype=np.int32); sums = np.zeros((9, 4), dtype=np.uint64)
+    args = (curve, _hp(pts), _hp(_fa(key["k1"])), _hp(_fa(key["k2"])), _hp(_fa(key["omega"])), int(key["power"]), _hp(commits), _hp(evals), _hp(pubs),
+            C.c_size_t(n_pub), C.c_size_t(n), _hp(coeff128), _hp(ch), _hp(sp), _hp(sk), _hp(valid), _hp(sums))
+    if ctx_handle is None:
+        _chk(load().cg_plonk_verify_scalars_host(*args))
+    else:
+        _chk(load().cg_plonk_verify_scalars(ctx_handle, *args))
+    return dict(challenges=ch, proof_scalars=sp, key_scalars=sk, valid=valid[:n].copy(), key_sums=sums)
+
+
+def plonk_verify_scalars_host(curve, key, commits, evals, pubs, coeff128=None):
+    """The Fiat-Shamir challenges and the scalars of n Plonk proofs under one key, on the host (the function the GPU lanes run).
+    key: dict(points=(8, point words) Qm..S3, k1, k2, omega, power); commits (n, 9, point words); evals (n, 6, 4); pubs (n, n_pub, 4);
+    coeff128 (optional): (n, 2) u64, canonical 128-bit integers multiplied into every scalar of their proof.
+    Returns dict(challenges (n, 6, 4): beta, gamma, alpha, xi, v, u; proof_scalars (n, 11, 4); key_scalars (n, 9, 4); valid (n); key_sums (9, 4))."""
+    return _plonk_verify_scalars(None, curve, key, commits, evals, pubs, coeff128)
 
 
 # ---- host-side mirror of the reference prover interface (libcogroth16_host.so, C++ over the C ABI) -----------------------
@@ -1219,6 +1263,88 @@ def plonk_prove_shamir_party(curve, zkey_path, threshold, pub, wit, net_table, r
     return dct, sec[0], _shamir_stats(rs, ps)
 
 
+def _plonk_proof_arrays(curve, proofs):
+    """(commits (n, 9, point words), evals (n, 6, 4)) of a list of proof dicts, or of a (commits, evals) pair of stacked arrays"""
+    nq = fq_limbs(curve)
+    if isinstance(proofs, tuple):
+        commits, evals = proofs
+    else:
+        proofs = list(proofs)
+        commits = np.stack([np.stack([p[k] for k in PLONK_COMMITS]) for p in proofs]) if proofs else np.zeros((0, 9, 2 * nq), dtype=np.uint64)
+        evals = np.stack([np.stack([p[k] for k in PLONK_EVALS]) for p in proofs]) if proofs else np.zeros((0, 6, 4), dtype=np.uint64)
+    commits = np.ascontiguousarray(commits, dtype=np.uint64).reshape(-1, 9, 2 * nq)
+    return commits, np.ascontiguousarray(evals, dtype=np.uint64).reshape(commits.shape[0], 6, 4)
+
+
+class PlonkVerifyingKey:
+    """Plonk verifying key (cgh_plonk_vk_*): points validated, the domain's root of unity checked against the library's own when the handle is opened"""
+    POINTS = ("Qm", "Ql", "Qr", "Qo", "Qc", "S1", "S2", "S3")
+
+    def __init__(self, curve, handle):
+        self.curve, self.h = curve, handle
+        info = (C.c_size_t * 3)()
+        _hchk(load_host().cgh_plonk_vk_info(self.h, info))
+        self.n_public, self.power = int(info[1]), int(info[2])
+
+    @classmethod
+    def from_json(cls, curve, path):
+        h = C.c_void_p()
+        _hchk(load_host().cgh_plonk_vk_from_json(curve, path.encode(), C.byref(h)))
+        return cls(curve, h)
+
+    @classmethod
+    def from_zkey(cls, curve, path):
+        h = C.c_void_p()
+        _hchk(load_host().cgh_plonk_vk_from_zkey(curve, path.encode(), C.byref(h)))
+        return cls(curve, h)
+
+    def close(self):
+        if self.h: load_host().cgh_plonk_vk_free(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def fields(self):
+        """dict of the key's fields: Qm .. S3, X_2 (packed affine, Montgomery), k1, k2, w, nPublic, power"""
+        nq = fq_limbs(self.curve)
+        out = np.zeros(20 * nq + 12, dtype=np.uint64)
+        _hchk(load_host().cgh_plonk_vk_fields(self.h, _hp(out)))
+        d = dict(zip(self.POINTS, out[:16 * nq].reshape(8, 2 * nq)))
+        d.update(X_2=out[16 * nq:20 * nq], k1=out[20 * nq:20 * nq + 4], k2=out[20 * nq + 4:20 * nq + 8], w=out[20 * nq + 8:], nPublic=self.n_public, power=self.power)
+        return d
+
+    def scalars_key(self):
+        """the key as plonk_verify_scalars_host / Context.plonk_verify_scalars take it"""
+        f = self.fields()
+        return dict(points=np.stack([f[k] for k in self.POINTS]), k1=f["k1"], k2=f["k2"], omega=f["w"], power=self.power)
+
+    def verify(self, proof, pub):
+        """one proof (the dict the prove entries return) on the host (cgh_plonk_verify); a wrong number of public inputs or a non-canonical one raises BackendError"""
+        commits, evals = _plonk_proof_arrays(self.curve, [proof])
+        pub = np.ascontiguousarray(pub, dtype=np.uint64).reshape(-1, 4)
+        ok = C.c_int32(0)
+        _hchk(load_host().cgh_plonk_verify(self.h, _hp(commits), _hp(evals), _hp(pub), C.c_size_t(pub.shape[0]), C.byref(ok)))
+        return bool(ok.value)
+
+    def verify_batch(self, proofs, pubs, seed=None, per_proof=False, device=0, timing=False):
+        """n proofs on the GPU with random 128-bit coefficients (cgh_plonk_verify_batch).  proofs: a list of proof dicts or a (commits, evals)
+        pair of stacked arrays; pubs: (n, n_public, 4).  Returns the verdict; with per_proof=True (verdict, flags); with timing=True the
+        five stage times in seconds are appended."""
+        commits, evals = _plonk_proof_arrays(self.curve, proofs)
+        n = commits.shape[0]
+        pubs = np.ascontiguousarray(pubs, dtype=np.uint64).reshape(n, self.n_public, 4) if n else np.zeros((0, self.n_public, 4), dtype=np.uint64)
+        ok = C.c_int32(0)
+        flags = np.zeros(max(n, 1), dtype=np.uint8) if per_proof else None
+        secs = (C.c_double * 5)()
+        _hchk(load_host().cgh_plonk_verify_batch_timed(int(device), self.h, _hp(commits), _hp(evals), _hp(pubs), C.c_size_t(pubs.shape[1]), C.c_size_t(n),
+                                                       None if seed is None else bytes(seed), C.byref(ok), _hp(flags), secs))
+        out = (bool(ok.value),) + ((flags[:n].astype(bool),) if per_proof else ()) + ((list(secs),) if timing else ())
+        return out[0] if len(out) == 1 else out
+
+
 class PlonkSession:
     """co-plonk proving session (cgh_plonk_session_*): the zkey is read once; p_tau (validated, with per-window tables), the q / sigma /
     Lagrange polynomials, the wire maps and the additions' level schedule stay on the device; proofs (rounds 1..5) read them there"""
@@ -1254,6 +1380,15 @@ class PlonkSession:
         _hchk(load_host().cgh_plonk_session_prove_plain(self.h, _hp(w), _hp(_pad_blind(blind)), _hp(commits), _hp(ev), _hp(ch), sec))
         dct = dict(zip(PLONK_COMMITS, commits)); dct.update(zip(PLONK_CHALLENGES, ch)); dct.update(zip(PLONK_EVALS, ev))
         return dct, sec[0]
+
+    def verify(self, proof, pub):
+        """Plonk::verify of a proof (the dict the prove entries return) against the session's own key (cgh_plonk_session_verify); pub = the
+        n_public public inputs, Montgomery"""
+        commits, evals = _plonk_proof_arrays(self.curve, [proof])
+        pub = self._rows("pub", pub, self.info["n_public"])
+        ok = C.c_int32(0)
+        _hchk(load_host().cgh_plonk_session_verify(self.h, _hp(commits), _hp(evals), _hp(pub), C.byref(ok)))
+        return bool(ok.value)
 
     def prove_rep3_party(self, pub, wit_a, wit_b, net_table, rand_table, blind_a=None, blind_b=None, streams_table=None):
         """ONE REP3 party through the callback ABI (cgh_plonk_session_prove_rep3_party); blind_a/blind_b None = drawn with rand() first.

@@ -1,5 +1,6 @@
 // C entry points: co-plonk (co-plonk/src/plonk.rs:133-271 drives round1..round5)
 #include "plonk.hpp"
+#include "plonk_verify.hpp"
 #include "capi_common.hpp"
 
 #include <chrono>
@@ -314,7 +315,8 @@ int32_t cgh_plonk_prove_shamir_party(int32_t device, int32_t curve, const char* 
 struct cgh_plonk_session {
     cg_ctx* ctx = nullptr;
     std::unique_ptr<cgh::PlonkResident> res;
-    std::mutex mu;
+    std::unique_ptr<cgh::PlonkVerifyingKey> vk;                                          // cgh_plonk_session_verify: prepared from the zkey's header at first use (under vk_mu)
+    std::mutex mu, vk_mu;
     ~cgh_plonk_session() { res.reset(); if (ctx) cg_ctx_destroy(ctx); }
 };
 namespace {
@@ -348,6 +350,15 @@ int32_t cgh_plonk_session_info(void* session, size_t* info) {
 int32_t cgh_plonk_session_close(void* session) {
     delete (cgh_plonk_session*)session;
     return 0;
+}
+int32_t cgh_plonk_session_verify(void* session, const uint64_t* commits, const uint64_t* evals, const uint64_t* pub, int32_t* ok) {
+    try {
+        cgh_plonk_session* s = plonk_session(session, "cgh_plonk_session_verify");
+        const cgh::PlonkZKey& z = s->res->z;
+        if (!commits || !evals || !ok || (z.n_public && !pub)) throw std::runtime_error("cgh_plonk_session_verify: null argument");
+        { std::lock_guard<std::mutex> l(s->vk_mu); if (!s->vk) s->vk.reset(new cgh::PlonkVerifyingKey(cgh::plonk_vk_from_zkey_data(z))); }
+        *ok = cgh::plonk_verify(*s->vk, (const uint8_t*)commits, evals, pub, z.n_public) ? 1 : 0; return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
 }
 int32_t cgh_plonk_session_prove_plain(void* session, const uint64_t* full_witness, const uint64_t* blind, uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds) {
     cgh_plonk_session* s = nullptr;

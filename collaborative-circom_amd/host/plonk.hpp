@@ -16,6 +16,7 @@ struct PlonkZKey {   // circom-types/src/plonk/zkey.rs:18-42 (the fields round 1
     Bytes p_tau;        // domain_size + 6 packed G1 points
     Fr k1, k2;          // verifying key, zkey.rs:328-356
     Bytes vk_g1;        // qm, ql, qr, qo, qc, s1, s2, s3 (8 packed G1 points)
+    Bytes x_2;          // [tau]_2 (packed G2 point): the verifier's (plonk_verify.hpp)
     std::vector<Fr> sigma_eval[3];   // 4 * domain_size evaluations of sigma1..3 (section 12, zkey.rs:116-135,170-180)
     std::vector<Fr> q_eval[5];       // qm, ql, qr, qo, qc on the extended domain (sections 7..11)
     std::vector<std::vector<Fr>> lagrange_eval;   // n_public polynomials on the extended domain (section 13)
@@ -46,6 +47,7 @@ static PlonkZKey read_plonk_zkey(int curve_id, const std::string& path) {   // z
     while (((size_t)1 << z.power) < z.domain_size) z.power++;
     h.bytes(z.k1.v, 32); h.bytes(z.k2.v, 32);
     z.vk_g1.resize(8 * c.aff(CG_G1)); h.bytes(z.vk_g1.data(), z.vk_g1.size());
+    z.x_2.resize(c.aff(CG_G2)); h.bytes(z.x_2.data(), z.x_2.size());
     {
         Cursor sg = section(12);
         for (int k = 0; k < 3; k++) {

@@ -424,6 +424,26 @@ int32_t cg_miller_batch(cg_ctx* ctx, int32_t curve, const void* h_g1, const void
 int32_t cg_miller_product(cg_ctx* ctx, int32_t curve, const void* h_g1, const void* h_g2, const void* h_scalars128, size_t n, void* h_out_fp12);
 int32_t cg_final_exp_check_batch(cg_ctx* ctx, int32_t curve, const void* h_fp12s, int32_t k, size_t n, const void* h_target_fp12, int32_t* ok);
 
+/* ---- Plonk verification, the per-proof layer (co-plonk/src/plonk.rs:47-271; csrc/plonk_verify.hpp) -----------------------
+ * plonk_verify_scalars: for each of n proofs under one key, the six Fiat-Shamir challenges (Keccak-256 transcripts) and the coefficients
+ * of the two G1 linear combinations A1, B1 with "proof accepted iff e(A1, X_2) e(-B1, G_2) = 1".  One GPU lane per proof; the _host twin
+ * runs the same function in a loop and needs no device.  Everything is Montgomery form, fully reduced (the caller checks); points packed affine.
+ *   key:      h_key_points = Qm, Ql, Qr, Qo, Qc, S1, S2, S3; h_k1, h_k2; h_omega = the 2^power-th root of unity
+ *   inputs:   h_commits n x 9 points (a, b, c, z, t1, t2, t3, wxi, wxiw); h_evals n x 6 (a, b, c, s1, s2, zw); h_pubs n x n_pub;
+ *             h_coeff128 (optional) n canonical little-endian 128-bit integers r_i: every one of proof i's 20 scalars is multiplied by r_i
+ *   outputs:  h_challenges n x 6 (beta, gamma, alpha, xi, v, u); h_proof_scalars n x 11 (of wxi, wxiw in A1, then of the nine commitments
+ *             in B1); h_key_scalars n x 9 (of Qm .. S3 and of the G1 generator in B1); h_valid n flags, 0 where xi hits one of the first
+ *             max(1, n_pub) domain points (the reference divides by zero there: reject); h_key_sums = the 9 sums of h_key_scalars over the proofs.
+ * g1_lincomb_batch: out[g] = sum_{k < k_terms} s[g, k] P[g, k], g < n_groups: packed affine G1 points in, Montgomery scalars, packed affine out.
+ * One GPU lane per term, 1 <= k_terms <= 64.  Equal, opposite and infinite summands and zero scalars are handled. */
+int32_t cg_plonk_verify_scalars(cg_ctx* ctx, int32_t curve, const void* h_key_points, const void* h_k1, const void* h_k2, const void* h_omega, int32_t power,
+                                const void* h_commits, const void* h_evals, const void* h_pubs, size_t n_pub, size_t n, const void* h_coeff128,
+                                void* h_challenges, void* h_proof_scalars, void* h_key_scalars, int32_t* h_valid, void* h_key_sums);
+int32_t cg_plonk_verify_scalars_host(int32_t curve, const void* h_key_points, const void* h_k1, const void* h_k2, const void* h_omega, int32_t power,
+                                     const void* h_commits, const void* h_evals, const void* h_pubs, size_t n_pub, size_t n, const void* h_coeff128,
+                                     void* h_challenges, void* h_proof_scalars, void* h_key_scalars, int32_t* h_valid, void* h_key_sums);
+int32_t cg_g1_lincomb_batch(cg_ctx* ctx, int32_t curve, const void* h_points, const void* h_scalars, size_t n_groups, int32_t k_terms, void* h_out_affine);
+
 /* ---- tooling (bench / tests; not on the prover path) ----------------------------------------------------------- */
 /* Builds, on the device, the table [(first + i) * G]_{i<n} of consecutive multiples of the group generator: valid,
  * pairwise distinct points with known discrete logs, used as synthetic zkey-sized bases. */

@@ -325,6 +325,9 @@ int32_t cgh_plonk_prove_shamir_party(int32_t device, int32_t curve, const char* 
 int32_t cgh_plonk_session_open(int32_t device, int32_t curve, const char* zkey_path, int32_t precompute, uint32_t flags, void** out_session);
 int32_t cgh_plonk_session_info(void* session, size_t* info);
 int32_t cgh_plonk_session_close(void* session);
+/* Plonk::verify with the verifying key taken from the session's zkey header (prepared at first use): what a party runs on the proof it has
+ * just opened.  commits / evals as the prove entries return them; pub = the n_public public inputs (without the leading one).  Host arithmetic. */
+int32_t cgh_plonk_session_verify(void* session, const uint64_t* commits, const uint64_t* evals, const uint64_t* pub, int32_t* ok);
 int32_t cgh_plonk_session_prove_plain(void* session, const uint64_t* full_witness, const uint64_t* blind,
                                       uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds);
 int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in, const uint64_t* wit_a, const uint64_t* wit_b,
@@ -356,6 +359,41 @@ int32_t cgh_synth_circuit(int32_t device, int32_t curve, int32_t log_m, uint64_t
  * 1-14, p_tau = n + 6 points) + .wtns: n_public >= 1 public-input rows, multiplication / addition / constant gates with fan-out, n_additions
  * additions in chains six deep (some over public inputs), identity permutation on the padding rows */
 int32_t cgh_synth_plonk_circuit(int32_t device, int32_t curve, int32_t log_n, uint64_t seed, uint32_t n_public, uint32_t n_additions, const char* zkey_path, const char* wtns_path);
+
+/* ---- Plonk verification (co-plonk/src/plonk.rs:133-271; host/plonk_verify.hpp) ---------------------------------------------
+ * A verifying-key handle holds nPublic, power, k1, k2, Qm, Ql, Qr, Qo, Qc, S1, S2, S3 and X_2 from a verification_key.json (the fields
+ * circom-types/src/plonk/verification_key.rs reads; `protocol` must be "plonk", `curve` the handle's) or from a plonk zkey's header.
+ * Opening one validates every point (cg_point_validate; the point at infinity is legal: Qr and Qc of small circuits) and the domain:
+ * `power` within the field's two-adicity, `w` equal to the library's own 2^power-th root of unity.  Anything else is an error status.
+ * info[3]: curve, n_public, power.  fields (for tools and tests that compare keys): Qm .. S3 (8 packed G1 points), X_2 (packed G2), k1, k2, w
+ * (Montgomery), back to back: the caller provides 20 q + 12 64-bit words, q = 4 (BN254) or 6 (BLS12-381) words per base-field element.
+ * A handle is immutable and may be used from several threads.
+ * A proof is its nine commitments a, b, c, z, t1, t2, t3, wxi, wxiw (packed affine G1) and its six evaluations a, b, c, s1, s2, zw
+ * (Montgomery), as the prove entries return them. */
+int32_t cgh_plonk_vk_from_json(int32_t curve, const char* path, void** out_vk);
+int32_t cgh_plonk_vk_from_zkey(int32_t curve, const char* path, void** out_vk);
+int32_t cgh_plonk_vk_info(void* vk, size_t* info);
+int32_t cgh_plonk_vk_fields(void* vk, uint64_t* out);
+int32_t cgh_plonk_vk_free(void* vk);
+/* One proof, on the host (no device): the challenges and scalars of cg_plonk_verify_scalars_host, 20 scalar multiplications, and
+ * *ok = 1 iff e(A1, X_2) e(-B1, G_2) = 1.  n_pub != nPublic, or a public input not below the modulus, is an ERROR status, not a verdict.
+ * A commitment with a coordinate not below q, off the curve or outside the subgroup, or an evaluation not below r, gives *ok = 0 (the
+ * reference's proof parser rejects them); so does a challenge xi on one of the first max(1, n_pub) domain points. */
+int32_t cgh_plonk_verify(void* vk, const uint64_t* commits, const uint64_t* evals, const uint64_t* pub, size_t n_pub, int32_t* ok);
+/* n_proofs proofs under one key on the GPU `device` (commits n x 9 points, evals n x 6, pubs n x n_pub): with r_0 = 1 and r_1.. 128-bit
+ * coefficients from ChaCha12 (seed32, or OS entropy when NULL; drawn as cgh_groth16_verify_batch draws them), *ok = 1 iff
+ *   e(sum_i r_i A1_i, X_2) e(-sum_i r_i B1_i, G_2) = 1
+ * after the on-curve and subgroup passes over the 9n commitments and the canonical checks of the evaluations: cg_plonk_verify_scalars with
+ * the coefficients, one cg_msm over the 2n A-side points, one over the 9n B-side points (the key's points and the generator are added on
+ * the host with the scalars summed over the proofs), two pairings for the whole batch.  A batch with an invalid proof is accepted with
+ * probability at most 2^-128 over the coefficients.  When the batch is rejected and per_proof is given, every proof is decided on its own
+ * on the GPU (cg_g1_lincomb_batch for A1_i and B1_i, two Miller loops and a final exponentiation per lane) and per_proof[i] = 1 / 0; an
+ * accepted batch sets every flag.  n_proofs == 0 accepts.  Errors as for cgh_plonk_verify.
+ * _timed: seconds[5] (optional) = point checks, scalar kernel, A-side MSM, B-side MSM, host tail. */
+int32_t cgh_plonk_verify_batch(int32_t device, void* vk, const uint64_t* commits, const uint64_t* evals, const uint64_t* pubs, size_t n_pub, size_t n_proofs,
+                               const uint8_t* seed32, int32_t* ok, uint8_t* per_proof);
+int32_t cgh_plonk_verify_batch_timed(int32_t device, void* vk, const uint64_t* commits, const uint64_t* evals, const uint64_t* pubs, size_t n_pub, size_t n_proofs,
+                                     const uint8_t* seed32, int32_t* ok, uint8_t* per_proof, double* seconds);
 
 #ifdef __cplusplus
 }
