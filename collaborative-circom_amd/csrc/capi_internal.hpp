@@ -3,6 +3,7 @@
 // capi_ntt.hip: the launch logic of the two kernel families).  Round 6: capi.hip was one 2 600-line unit; a pure move.
 #pragma once
 #include "common.hpp"
+#include "launchers.hpp"   // the launchers of msm_inst_*.hip / fr_inst_*.hip, MsmSortPtrs, scratch sizes
 #include "curve.hpp"
 #include "subgroup.hpp"
 #include "host_ec64.hpp"
@@ -18,69 +19,6 @@
 
 using namespace cg;
 
-// launchers living in msm_inst_*.hip / fr_inst_*.hip (explicit instantiations)
-namespace cg {
-struct MsmSortPtrs { const uint32_t* sorted; const uint32_t* offsets; const uint32_t* counts; uint32_t cap; const uint32_t* overflow; };
-template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, char* scratch, MsmSortPtrs* out, hipEvent_t* evs);
-template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, uint32_t cap, char* scratch, MsmSortPtrs* out, hipEvent_t* evs);
-inline size_t msm_sort_direct_scratch_bytes(size_t n, int c, int nwin, int shared, uint32_t cap) {
-    const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
-    return align_up(nbuckets * cap * 4) + 2 * align_up(nbuckets * 4) + align_up(((nbuckets + 2047) / 2048) * 4) + 256;
-}
-template <class F> int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* evs, uint32_t chunk_request, bool g2_slices);
-template <class F> int msm_reduce_batch(hipStream_t st2, const MsmRedSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* ev_merged, int n_merged,
-                                        hipEvent_t* evs, uint32_t chunk_request);
-template <class F> size_t msm_acc_scratch_bytes(size_t n, int c, int nwin, bool shared, uint32_t chunk_request);
-template <class F> int precompute_window_launch(hipStream_t st, const Affine<F>* d_src, Affine<F>* d_dst, size_t n, int c);
-template <class F> int check_on_curve_launch(hipStream_t st, const Affine<F>* d_pts, size_t n, const F& b, unsigned long long* d_counters);
-template <class F, class Fr> int check_subgroup_launch(hipStream_t st, const Affine<F>* d_pts, size_t n, unsigned long long* d_counters);
-template <class F> int check_subgroup_fast_launch(hipStream_t st, const Affine<F>* d_pts, size_t n, const FastSubgroup<F>& c, unsigned long long* d_counters);
-inline size_t msm_sort_scratch_bytes(size_t n, int c, int nwin) {   // must match fr_impl.hpp
-    const size_t nbuckets = (size_t)nwin << (c - 1);
-    const size_t entries = (size_t)nwin * n;
-    return 2 * align_up(entries * 4) + 3 * align_up(nbuckets * 4) + align_up(((nbuckets + 2047) / 2048) * 4) + align_up(entries * 8) + 2 * align_up(4096 * 4) + 256;
-}
-template <class F> int pack_bases_launch(hipStream_t st, const uint8_t* d_raw, size_t n, size_t stride, long inf_off, Affine<F>* d_dst);
-template <class F> int gather_points_launch(hipStream_t st, Affine<F>* d_dst, const Affine<F>* d_src, const uint32_t* d_idx, size_t n);
-template <class Fr> int launch_vec_gather_idx(hipStream_t st, Fr* out, const Fr* in, const uint32_t* idx, size_t n, uint32_t base);
-template <class F> int synth_points_launch(hipStream_t st, const XYZZ<F>* d_lo, const XYZZ<F>* d_hi, int log_t, size_t n, Affine<F>* d_out);
-template <class F, class Fr> int fixed_base_mul_launch(hipStream_t st, const Affine<F>& g, const Fr* d_scalars, size_t n, Affine<F>* d_tab, Affine<F>* d_out);
-template <class Fr> int launch_vec_binary(hipStream_t st, int op, Fr* out, const Fr* a, const Fr* b, size_t n);
-int chacha12_fr_rand_launch(hipStream_t st, const uint32_t* key8, const uint32_t* mod8, int modulus_bits, uint64_t word_pos, uint64_t n_pairs, uint64_t n,
-                            void* d_cand, uint32_t* d_tiles, unsigned long long* d_result, void* d_out);   // chacha_rand.hip
-template <class Fr> int launch_rep3_mul_local(hipStream_t st, Fr* out, const Fr* aa, const Fr* ab, const Fr* ba, const Fr* bb, const Fr* mask, size_t n);
-template <class Fr> int launch_distribute_powers(hipStream_t st, Fr* v, size_t n, const Fr* lo, const Fr* hi, int log_lo);
-template <class Fr> int launch_vec_count_noncanonical(hipStream_t st, const Fr* v, size_t n, unsigned long long* n_bad);
-template <class Fr> int launch_vec_fill(hipStream_t st, Fr* v, size_t n, const Fr& value);
-template <class Fr> int launch_vec_affine(hipStream_t st, Fr* out, const Fr* a, size_t n, const Fr& c, const Fr& d);
-template <class Fr> int launch_vec_gather_strided(hipStream_t st, Fr* out, const Fr* in, size_t n, size_t offset, size_t stride);
-template <class Fr> int launch_vec_lincomb(hipStream_t st, Fr* out, long long out_off, long long out_stride, size_t n, const LincombArgs<Fr>& a);
-template <class Fr> int launch_shamir_share(hipStream_t st, const Fr* secrets, const Fr* coeffs, long long coeff_off, long long coeff_stride, size_t n, int degree,
-                                            const ShareOuts<Fr>& o, long long out_off, long long out_stride);
-template <class Fr> int launch_plonk_r2_factors(hipStream_t st, const PlonkR2Args<Fr>& g, size_t n);
-template <class Fr> int launch_prefix_scan(hipStream_t st, int op, Fr* out, const Fr* in, size_t n, Fr* scratch);
-template <class Fr> int launch_vec_inverse(hipStream_t st, Fr* out, const Fr* in, size_t n);
-template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* order, size_t n, const uint32_t* ids, const Fr* coeffs, const Fr* pub, uint32_t n_inputs, int pc,
-                                               Fr* ext_a, Fr* ext_b, size_t n_priv);
-template <class Fr> int launch_plonk_r3_blind(hipStream_t st, const PlonkBlindArgs<Fr>& g, size_t n);
-template <class Fr> int launch_plonk_r3_perm(hipStream_t st, const PlonkPermArgs<Fr>& g, size_t n);
-template <class Fr> int launch_plonk_r3_gate(hipStream_t st, const PlonkGateArgs<Fr>& g, size_t n);
-template <class Fr> int launch_plonk_mul4_tail(hipStream_t st, const PlonkMul4Args<Fr>& g, size_t n);
-template <class Fr> int launch_plonk_r3_t(hipStream_t st, const PlonkTArgs<Fr>& g, size_t n);
-template <class Fr> int launch_plonk_r3_divide(hipStream_t st, const PlonkDivArgs<Fr>& g, size_t n);
-template <class Fr> int launch_spmv_csr(hipStream_t st, const uint32_t* row_ptr, const uint32_t* col, const Fr* coeff, size_t n_rows, const Fr* pub,
-                                        uint32_t n_inputs, int party, const Fr* wit_a, const Fr* wit_b, Fr* out_a, Fr* out_b);
-template <class Fr> int launch_build_twiddles(hipStream_t st, Fr* tw, size_t m, int log_m, const Fr* lo, const Fr* hi, int log_lo);
-template <class Fr> int launch_build_twiddles_lazy(hipStream_t st, void* tw, size_t m, int log_m, const Fr* lo, const Fr* hi, int log_lo, const Fr& c32);
-template <class Fr> int launch_ntt_ct_pass(hipStream_t st, bool first, NttVecs src, NttVecs dst, int nvec, size_t n, int log_m, int s0, int k, int t, const void* tw);
-template <class Fr> int launch_build_twiddles_lazy_natural(hipStream_t st, void* tw, size_t m, const Fr* lo, const Fr* hi, int log_lo, const Fr& c32);
-template <class Fr> int launch_ntt_dit_pass(hipStream_t st, bool first, bool last, NttVecs out, NttVecs tmp, int nvec, size_t n, int log_m, int s0, int k, int t, const void* tw,
-                                            const Fr* c_lo, const Fr* c_hi, int log_lo, const Fr& c32);
-template <class Fr> int launch_bitrev_finish_lazy(hipStream_t st, NttVecs dst, NttVecs src, int nvec, size_t n, int log_m, const Fr* scale, const Fr* c_lo, const Fr* c_hi, int log_lo);
-template <class Fr> int launch_ntt_dif_pass(hipStream_t st, NttVecs src, NttVecs dst, int nvec, size_t n, int log_m, int s0, int k, int t, const Fr* tw);
-template <class Fr> int launch_bitrev_scale(hipStream_t st, NttVecs dst, NttVecs src, int nvec, size_t n, int log_m, const Fr* scale, const Fr* c_lo, const Fr* c_hi, int log_lo);
-}  // namespace cg
-
 // every device allocation of the library outside cg_dev_alloc: hipMalloc that, when the device is out of memory, gives back the blocks
 // parked by cg_dev_free on the current device (up to CG_DEV_CACHE_MB of them) and tries once more
 hipError_t hip_malloc_flush(void** p, size_t bytes);
@@ -94,7 +32,8 @@ struct Arena {
     void* take(size_t bytes) { void* p = base + used; used += align_up(bytes); return p; }
 };
 
-struct TwKey { int curve; int log_m; uint32_t gen[8]; int kind = 0;   // kind 0: stage-major packed tables (DIF passes), 1: bit-reversed limb-form table (lazy passes)
+enum { TW_BITREV = 1, TW_NATURAL = 2 };   // tw[i] = 32 w^bitrev(i) (k_ntt_ct_pass) / tw[e] = 32 w^e (k_ntt_dit_pass)
+struct TwKey { int curve; int log_m; uint32_t gen[8]; int kind = 0;   // order of a limb-form twiddle table (TW_*); 0 in the coset keys
     bool operator<(const TwKey& o) const { if (curve != o.curve) return curve < o.curve; if (log_m != o.log_m) return log_m < o.log_m; if (kind != o.kind) return kind < o.kind; return memcmp(gen, o.gen, sizeof gen) < 0; } };
 struct CosetKey { TwKey k; uint32_t scale[8]; bool operator<(const CosetKey& o) const { if (k < o.k) return true; if (o.k < k) return false; return memcmp(scale, o.scale, sizeof scale) < 0; } };
 struct CosetTables { void* lo; void* hi; int log_lo; };

@@ -48,83 +48,40 @@ void shared_twiddles_release(int device, const TwKey& key) {
 }
 namespace {
 
+// constants of the lazy passes: 32 in Montgomery form (the lazy core divides by 2^261, the ABI's R is 2^256) and 1 / 2^log_m
+template <class Fr> Fr mont32() { Fr c = Fr::one(); for (int i = 0; i < 5; i++) c = c + c; return c; }
+template <class Fr> Fr inv_pow2(int log_m) {
+    uint32_t e[Fr::N] = {0}; e[log_m / 32] = 1u << (log_m % 32);
+    Fr nn; for (int i = 0; i < Fr::N; i++) nn.v[i] = e[i];
+    return fp_inverse(nn.to_mont());
+}
+
+// limb-form twiddle table of m/2 entries (ntt_kernels.hpp): tw[i] = 32 * w^bitrev(i) for the Cooley-Tukey passes, or, `natural`,
+// tw[e] = 32 * w^e for the decimation-in-time passes
 template <class Fr>
-int get_twiddles(cg_ctx* ctx, int curve, int log_m, const Fr& w, const Fr** out) {
-    TwKey key; key.curve = curve; key.log_m = log_m; memcpy(key.gen, w.v, sizeof key.gen);
+int get_twiddles_lazy(cg_ctx* ctx, int curve, int log_m, const Fr& w, bool natural, const void** out) {
+    TwKey key; key.curve = curve; key.log_m = log_m; key.kind = natural ? TW_NATURAL : TW_BITREV; memcpy(key.gen, w.v, sizeof key.gen);
     auto it = ctx->twiddles.find(key);
-    if (it != ctx->twiddles.end()) { *out = (const Fr*)it->second; return 0; }
-    if (void* shared = shared_twiddles_acquire(ctx->device, key)) { ctx->twiddles[key] = shared; *out = (const Fr*)shared; return 0; }
+    if (it != ctx->twiddles.end()) { *out = it->second; return 0; }
+    if (void* shared = shared_twiddles_acquire(ctx->device, key)) { ctx->twiddles[key] = shared; *out = shared; return 0; }
     const size_t m = (size_t)1 << log_m;
     const int log_lo = std::min(11, std::max(0, log_m - 1));
     const size_t hi_n = std::max<size_t>(1, (m / 2) >> log_lo);
     std::vector<Fr> lo, hi;
     host_pow_tables(w, Fr::one(), log_lo, hi_n, lo, hi);
-    Fr *d_lo = nullptr, *d_hi = nullptr, *d_tw = nullptr;
+    Fr *d_lo = nullptr, *d_hi = nullptr; void* d_tw = nullptr;
+    const size_t bytes = lazy29_bytes(std::max<size_t>(m / 2, 1));
     HIPCHK(hip_malloc_flush((void**)&d_lo, lo.size() * sizeof(Fr)));
     HIPCHK(hip_malloc_flush((void**)&d_hi, hi.size() * sizeof(Fr)));
-    HIPCHK(hip_malloc_flush((void**)&d_tw, std::max<size_t>(m - 1, 1) * sizeof(Fr)));
+    HIPCHK(hip_malloc_flush(&d_tw, bytes));
     HIPCHK(hipMemcpyAsync(d_lo, lo.data(), lo.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipMemcpyAsync(d_hi, hi.data(), hi.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    { int rc = launch_build_twiddles<Fr>(ctx->stream, d_tw, m, log_m, d_lo, d_hi, log_lo); if (rc) return rc; }
+    {
+        const int rc = natural ? launch_build_twiddles_lazy_natural<Fr>(ctx->stream, d_tw, m, d_lo, d_hi, log_lo, mont32<Fr>())
+                               : launch_build_twiddles_lazy<Fr>(ctx->stream, d_tw, m, log_m, d_lo, d_hi, log_lo, mont32<Fr>());
+        if (rc) return rc;
+    }
     HIPCHK(hipStreamSynchronize(ctx->stream));   // lo/hi host vectors and temporaries die here
-    HIPCHK(hipFree(d_lo)); HIPCHK(hipFree(d_hi));
-    d_tw = (Fr*)shared_twiddles_publish(ctx->device, key, d_tw, std::max<size_t>(m - 1, 1) * sizeof(Fr));
-    ctx->twiddles[key] = d_tw;
-    *out = d_tw;
-    return 0;
-}
-
-// limb-form table of the lazy passes: tw[i] = 32 * w^bitrev(i), i < m/2 (ntt_kernels.hpp)
-template <class Fr>
-int get_twiddles_lazy(cg_ctx* ctx, int curve, int log_m, const Fr& w, const void** out) {
-    TwKey key; key.curve = curve; key.log_m = log_m; key.kind = 1; memcpy(key.gen, w.v, sizeof key.gen);
-    auto it = ctx->twiddles.find(key);
-    if (it != ctx->twiddles.end()) { *out = it->second; return 0; }
-    if (void* shared = shared_twiddles_acquire(ctx->device, key)) { ctx->twiddles[key] = shared; *out = shared; return 0; }
-    const size_t m = (size_t)1 << log_m;
-    const int log_lo = std::min(11, std::max(0, log_m - 1));
-    const size_t hi_n = std::max<size_t>(1, (m / 2) >> log_lo);
-    std::vector<Fr> lo, hi;
-    host_pow_tables(w, Fr::one(), log_lo, hi_n, lo, hi);
-    Fr c32 = Fr::one(); for (int i = 0; i < 5; i++) c32 = c32 + c32;
-    Fr *d_lo = nullptr, *d_hi = nullptr; void* d_tw = nullptr;
-    const size_t bytes = lazy29_bytes(std::max<size_t>(m / 2, 1));
-    HIPCHK(hip_malloc_flush((void**)&d_lo, lo.size() * sizeof(Fr)));
-    HIPCHK(hip_malloc_flush((void**)&d_hi, hi.size() * sizeof(Fr)));
-    HIPCHK(hip_malloc_flush(&d_tw, bytes));
-    HIPCHK(hipMemcpyAsync(d_lo, lo.data(), lo.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_hi, hi.data(), hi.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    { int rc = launch_build_twiddles_lazy<Fr>(ctx->stream, d_tw, m, log_m, d_lo, d_hi, log_lo, c32); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(d_lo)); HIPCHK(hipFree(d_hi));
-    d_tw = shared_twiddles_publish(ctx->device, key, d_tw, bytes);
-    ctx->twiddles[key] = d_tw;
-    *out = d_tw;
-    return 0;
-}
-
-// natural-order limb-form table of the decimation-in-time passes: tw[e] = 32 * w^e, e < m/2 (ntt_kernels.hpp, k_ntt_dit_pass)
-template <class Fr>
-int get_twiddles_lazy_natural(cg_ctx* ctx, int curve, int log_m, const Fr& w, const void** out) {
-    TwKey key; key.curve = curve; key.log_m = log_m; key.kind = 2; memcpy(key.gen, w.v, sizeof key.gen);
-    auto it = ctx->twiddles.find(key);
-    if (it != ctx->twiddles.end()) { *out = it->second; return 0; }
-    if (void* shared = shared_twiddles_acquire(ctx->device, key)) { ctx->twiddles[key] = shared; *out = shared; return 0; }
-    const size_t m = (size_t)1 << log_m;
-    const int log_lo = std::min(11, std::max(0, log_m - 1));
-    const size_t hi_n = std::max<size_t>(1, (m / 2) >> log_lo);
-    std::vector<Fr> lo, hi;
-    host_pow_tables(w, Fr::one(), log_lo, hi_n, lo, hi);
-    Fr c32 = Fr::one(); for (int i = 0; i < 5; i++) c32 = c32 + c32;
-    Fr *d_lo = nullptr, *d_hi = nullptr; void* d_tw = nullptr;
-    const size_t bytes = lazy29_bytes(std::max<size_t>(m / 2, 1));
-    HIPCHK(hip_malloc_flush((void**)&d_lo, lo.size() * sizeof(Fr)));
-    HIPCHK(hip_malloc_flush((void**)&d_hi, hi.size() * sizeof(Fr)));
-    HIPCHK(hip_malloc_flush(&d_tw, bytes));
-    HIPCHK(hipMemcpyAsync(d_lo, lo.data(), lo.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(d_hi, hi.data(), hi.size() * sizeof(Fr), hipMemcpyHostToDevice, ctx->stream));
-    { int rc = launch_build_twiddles_lazy_natural<Fr>(ctx->stream, d_tw, m, d_lo, d_hi, log_lo, c32); if (rc) return rc; }
-    HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipFree(d_lo)); HIPCHK(hipFree(d_hi));
     d_tw = shared_twiddles_publish(ctx->device, key, d_tw, bytes);
     ctx->twiddles[key] = d_tw;
@@ -159,7 +116,7 @@ int get_coset_tables(cg_ctx* ctx, int curve, int log_m, const Fr& g, const Fr& s
 }
 
 struct NttPass { int s0, k, t; };
-std::vector<NttPass> ntt_plan(int log_m, int tile_log = NTT_TILE_LOG) {
+std::vector<NttPass> ntt_plan(int log_m, int tile_log) {
     std::vector<NttPass> plan;
     const int k_last = std::min(log_m, tile_log);
     const int rest = log_m - k_last;
@@ -176,63 +133,35 @@ std::vector<NttPass> ntt_plan(int log_m, int tile_log = NTT_TILE_LOG) {
     return plan;
 }
 
+int ntt_lazy_tile() {                                     // CG_NTT_TILE (tuning knob): log2 of the elements per LDS tile
+    static const int tile = [] { const char* e = tune_env("CG_NTT_TILE"); const int v = e ? atoi(e) : NTT_TILE_LOG_LAZY; return std::min(NTT_TILE_LOG, std::max(8, v)); }();
+    return tile;
+}
+
+// lazy Cooley-Tukey passes (ntt_kernels.hpp): packed vectors -> limb-form scratch -> ... -> permutation back into the vectors,
+// which multiplies by 32 * (1/m) * coset power
 template <class Fr>
 int ntt_run(cg_ctx* ctx, int curve, void* const* d_vecs, int k, size_t n, const Fr& gen, bool inverse, const Fr* coset, size_t arena_off) {
     const int log_m = log2_floor(n);
     if (((size_t)1 << log_m) != n) return fail(CG_ERR_ARG, "NTT length must be a power of two");
     if (k < 1 || k > NTT_MAX_VECS) return fail(CG_ERR_ARG, "k out of range");
     if (n == 1) return 0;
+    if (!inverse && coset) return fail(CG_ERR_ARG, "coset_gen is only supported with inverse != 0");
     const Fr w = inverse ? fp_inverse(gen) : gen;
-    static const bool legacy = tune_env("CG_NTT_DIF") != nullptr;                 // A/B knob: the canonical DIF passes
-    if (!legacy) {
-        // lazy Cooley-Tukey passes (ntt_kernels.hpp): packed vectors -> limb-form scratch -> ... -> permutation back into the vectors,
-        // which multiplies by 32 * (1/m) * coset power (32: the lazy core divides by 2^261, the ABI's R is 2^256)
-        if (!inverse && coset) return fail(CG_ERR_ARG, "coset_gen is only supported with inverse != 0");
-        const void* twl = nullptr;
-        int rc = get_twiddles_lazy<Fr>(ctx, curve, log_m, w, &twl);
-        if (rc) return rc;
-        NttVecs data{}, tmp{};
-        for (int j = 0; j < k; j++) { data.p[j] = d_vecs[j]; tmp.p[j] = ctx->ntt_arena.base + arena_off + (size_t)j * lazy29_bytes(n); }
-        hipStream_t st = ctx->stream;
-        bool first = true;
-        static const int lazy_tile = [] { const char* e = tune_env("CG_NTT_TILE"); const int v = e ? atoi(e) : NTT_TILE_LOG_LAZY; return std::min(NTT_TILE_LOG, std::max(8, v)); }();   // tuning knob
-        for (const NttPass& p : ntt_plan(log_m, lazy_tile)) { rc = launch_ntt_ct_pass<Fr>(st, first, first ? data : tmp, tmp, k, n, log_m, p.s0, p.k, p.t, twl); if (rc) return rc; first = false; }
-        Fr scale32 = Fr::one(); for (int i = 0; i < 5; i++) scale32 = scale32 + scale32;
-        if (inverse) {
-            uint32_t e[Fr::N] = {0}; e[log_m / 32] = 1u << (log_m % 32);
-            Fr nn; for (int i = 0; i < Fr::N; i++) nn.v[i] = e[i];
-            scale32 = scale32 * fp_inverse(nn.to_mont());
-        }
-        CosetTables t;
-        const Fr* d_scale = nullptr; const Fr* c_lo = nullptr; const Fr* c_hi = nullptr; int log_lo = 0;
-        if (coset) { rc = get_coset_tables<Fr>(ctx, curve, log_m, *coset, scale32, &t); if (rc) return rc; c_lo = (const Fr*)t.lo; c_hi = (const Fr*)t.hi; log_lo = t.log_lo; }
-        else { rc = get_coset_tables<Fr>(ctx, curve, 0, Fr::one(), scale32, &t); if (rc) return rc; d_scale = (const Fr*)t.lo; }
-        return launch_bitrev_finish_lazy<Fr>(st, data, tmp, k, n, log_m, d_scale, c_lo, c_hi, log_lo);
-    }
-    const Fr* tw = nullptr;
-    int rc = get_twiddles<Fr>(ctx, curve, log_m, w, &tw);
+    const void* twl = nullptr;
+    int rc = get_twiddles_lazy<Fr>(ctx, curve, log_m, w, false, &twl);
     if (rc) return rc;
     NttVecs data{}, tmp{};
-    for (int j = 0; j < k; j++) { data.p[j] = d_vecs[j]; tmp.p[j] = ctx->ntt_arena.base + arena_off + (size_t)j * n * sizeof(Fr); }
+    for (int j = 0; j < k; j++) { data.p[j] = d_vecs[j]; tmp.p[j] = ctx->ntt_arena.base + arena_off + (size_t)j * lazy29_bytes(n); }
     hipStream_t st = ctx->stream;
-    {   // first pass reads the caller's vectors and writes the scratch copies; later passes run in the scratch copies
-        bool first = true;
-        for (const NttPass& p : ntt_plan(log_m)) { rc = launch_ntt_dif_pass<Fr>(st, first ? data : tmp, tmp, k, n, log_m, p.s0, p.k, p.t, tw); if (rc) return rc; first = false; }
-    }
+    bool first = true;
+    for (const NttPass& p : ntt_plan(log_m, ntt_lazy_tile())) { rc = launch_ntt_ct_pass<Fr>(st, first, first ? data : tmp, tmp, k, n, log_m, p.s0, p.k, p.t, twl); if (rc) return rc; first = false; }
+    const Fr scale32 = inverse ? mont32<Fr>() * inv_pow2<Fr>(log_m) : mont32<Fr>();
+    CosetTables t;
     const Fr* d_scale = nullptr; const Fr* c_lo = nullptr; const Fr* c_hi = nullptr; int log_lo = 0;
-    if (inverse) {
-        Fr ninv = Fr::one();   // n^-1: halve log_m times  (x/2 = (x + (x odd ? p : 0)) >> 1 in Montgomery form as well)
-        {
-            uint32_t e[Fr::N] = {0}; e[log_m / 32] = 1u << (log_m % 32);
-            Fr nn; for (int i = 0; i < Fr::N; i++) nn.v[i] = e[i];
-            ninv = fp_inverse(nn.to_mont());
-        }
-        CosetTables t;
-        if (coset) { rc = get_coset_tables<Fr>(ctx, curve, log_m, *coset, ninv, &t); if (rc) return rc; c_lo = (const Fr*)t.lo; c_hi = (const Fr*)t.hi; log_lo = t.log_lo; }
-        else { rc = get_coset_tables<Fr>(ctx, curve, 0, Fr::one(), ninv, &t); if (rc) return rc; d_scale = (const Fr*)t.lo; }
-    } else if (coset) return fail(CG_ERR_ARG, "coset_gen is only supported with inverse != 0");
-    // the permutation brings the result back: tmp -> data (natural order), fused with 1/m and the coset powers
-    return launch_bitrev_scale<Fr>(st, data, tmp, k, n, log_m, d_scale, c_lo, c_hi, log_lo);
+    if (coset) { rc = get_coset_tables<Fr>(ctx, curve, log_m, *coset, scale32, &t); if (rc) return rc; c_lo = (const Fr*)t.lo; c_hi = (const Fr*)t.hi; log_lo = t.log_lo; }
+    else { rc = get_coset_tables<Fr>(ctx, curve, 0, Fr::one(), scale32, &t); if (rc) return rc; d_scale = (const Fr*)t.lo; }
+    return launch_bitrev_finish_lazy<Fr>(st, data, tmp, k, n, log_m, d_scale, c_lo, c_hi, log_lo);
 }
 
 // v <- NTT_w( g^i * (iNTT_w v)_i ): the inverse transform's passes leave the coefficients bit-reversed in limb-form scratch, the
@@ -244,18 +173,15 @@ int ntt_coset_pair_run(cg_ctx* ctx, int curve, void* const* d_vecs, int k, size_
     if (k < 1 || k > NTT_MAX_VECS) return fail(CG_ERR_ARG, "k out of range");
     if (n == 1) return 0;                                                       // both transforms and g^0 are the identity
     const void* tw_inv = nullptr; const void* tw_fwd = nullptr;
-    int rc = get_twiddles_lazy<Fr>(ctx, curve, log_m, fp_inverse(gen), &tw_inv); if (rc) return rc;
-    rc = get_twiddles_lazy_natural<Fr>(ctx, curve, log_m, gen, &tw_fwd); if (rc) return rc;
-    Fr c32 = Fr::one(); for (int i = 0; i < 5; i++) c32 = c32 + c32;
-    uint32_t e[Fr::N] = {0}; e[log_m / 32] = 1u << (log_m % 32);
-    Fr nn; for (int i = 0; i < Fr::N; i++) nn.v[i] = e[i];
+    int rc = get_twiddles_lazy<Fr>(ctx, curve, log_m, fp_inverse(gen), false, &tw_inv); if (rc) return rc;
+    rc = get_twiddles_lazy<Fr>(ctx, curve, log_m, gen, true, &tw_fwd); if (rc) return rc;
+    const Fr c32 = mont32<Fr>();
     CosetTables ct;
-    rc = get_coset_tables<Fr>(ctx, curve, log_m, coset, c32 * fp_inverse(nn.to_mont()), &ct); if (rc) return rc;
+    rc = get_coset_tables<Fr>(ctx, curve, log_m, coset, c32 * inv_pow2<Fr>(log_m), &ct); if (rc) return rc;
     NttVecs data{}, tmp{};
     for (int j = 0; j < k; j++) { data.p[j] = d_vecs[j]; tmp.p[j] = ctx->ntt_arena.base + arena_off + (size_t)j * lazy29_bytes(n); }
     hipStream_t st = ctx->stream;
-    static const int lazy_tile = [] { const char* e_ = tune_env("CG_NTT_TILE"); const int v = e_ ? atoi(e_) : NTT_TILE_LOG_LAZY; return std::min(NTT_TILE_LOG, std::max(8, v)); }();
-    const std::vector<NttPass> plan = ntt_plan(log_m, lazy_tile);
+    const std::vector<NttPass> plan = ntt_plan(log_m, ntt_lazy_tile());
     bool first = true;
     for (const NttPass& p : plan) { rc = launch_ntt_ct_pass<Fr>(st, first, first ? data : tmp, tmp, k, n, log_m, p.s0, p.k, p.t, tw_inv); if (rc) return rc; first = false; }
     for (size_t i = plan.size(); i-- > 0;) {
@@ -285,8 +211,6 @@ int32_t cg_ntt_dev(cg_ctx* ctx, int32_t curve, void* const* d_vecs, int32_t k, s
 int32_t cg_ntt_coset_pair_dev(cg_ctx* ctx, int32_t curve, void* const* d_vecs, int32_t k, size_t n, const void* h_group_gen, const void* h_coset_gen) {
     if (!ctx || !d_vecs || !h_group_gen || !h_coset_gen) return fail(CG_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(ctx->device));
-    static const bool two_calls = tune_env("CG_NTT_NO_PAIR") != nullptr;         // A/B knob: the two separate transforms
-    if (two_calls) { int rc = cg_ntt_dev(ctx, curve, d_vecs, k, n, h_group_gen, 1, h_coset_gen); return rc ? rc : cg_ntt_dev(ctx, curve, d_vecs, k, n, h_group_gen, 0, nullptr); }
     return with_fr(curve, [&](auto tag) -> int {
         typedef decltype(tag) Fr;
         Fr gen, cos; copy_in(gen, h_group_gen); copy_in(cos, h_coset_gen);

@@ -55,7 +55,7 @@ struct PerDeviceOnce {
     bool pending() const { const int d = dev(); return d < 0 || !done[d].load(std::memory_order_acquire); }
     void mark() { const int d = dev(); if (d >= 0) done[d].store(true, std::memory_order_release); }
 };
-// the same for call sites that launch one of several kernels of ONE pointer type (the variants of k_msm_accumulate_pf): keyed by function and
+// the same for call sites that launch one of several kernels of ONE pointer type (k_msm_accumulate_pf and k_msm_accumulate, per accumulator policy): keyed by function and
 // device, set under the lock (a second thread launches only after the first one's call has returned), raised when a larger size is asked for
 inline int ensure_dynamic_lds(const void* fn, size_t bytes);
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }

@@ -1,6 +1,6 @@
 // Launch side of the scalar-field kernels (vec_kernels.hpp, ntt_kernels.hpp); instantiated per field in fr_inst_*.hip.
 #pragma once
-#include "common.hpp"
+#include "launchers.hpp"
 #include "ntt_kernels.hpp"
 #include "vec_kernels.hpp"
 #include "plonk_kernels.hpp"
@@ -124,19 +124,6 @@ template <class Fr> int launch_spmv_csr(hipStream_t st, const uint32_t* row_ptr,
     HIPCHK(hipGetLastError());
     return 0;
 }
-template <class Fr> int launch_build_twiddles(hipStream_t st, Fr* tw, size_t m, int log_m, const Fr* lo, const Fr* hi, int log_lo) {
-    if (m > 1) hipLaunchKernelGGL((k_build_twiddles<Fr>), dim3(grid_for(m - 1)), dim3(256), 0, st, tw, m, log_m, lo, hi, log_lo);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
-template <class Fr> int launch_ntt_dif_pass(hipStream_t st, NttVecs src, NttVecs dst, int nvec, size_t n, int log_m, int s0, int k, int t, const Fr* tw) {
-    static PerDeviceOnce attr_set;
-    if (attr_set.pending()) { HIPCHK(hipFuncSetAttribute((const void*)k_ntt_dif_pass<Fr>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536)); attr_set.mark(); }
-    const int E = 1 << (k + t);
-    hipLaunchKernelGGL((k_ntt_dif_pass<Fr>), dim3((unsigned)(n / E), nvec), dim3(NTT_THREADS), (size_t)E * 32, st, src, dst, log_m, s0, k, t, tw);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 template <class Fr> int launch_build_twiddles_lazy(hipStream_t st, void* tw, size_t m, int log_m, const Fr* lo, const Fr* hi, int log_lo, const Fr& c32) {
     if (m > 1) hipLaunchKernelGGL((k_build_twiddles_lazy<Fr>), dim3(grid_for(m / 2)), dim3(256), 0, st, tw, m / 2, log_m, lo, hi, log_lo, c32);
     HIPCHK(hipGetLastError());
@@ -187,28 +174,13 @@ template <class Fr> int launch_bitrev_finish_lazy(hipStream_t st, NttVecs dst, N
     HIPCHK(hipGetLastError());
     return 0;
 }
-template <class Fr> int launch_bitrev_scale(hipStream_t st, NttVecs dst, NttVecs src, int nvec, size_t n, int log_m, const Fr* scale, const Fr* c_lo, const Fr* c_hi, int log_lo) {
-    if (log_m >= 2 * BITREV_B)
-        hipLaunchKernelGGL((k_bitrev_scale<Fr>), dim3((unsigned)(n >> (2 * BITREV_B)), nvec), dim3(256), 0, st, dst, src, log_m, scale, c_lo, c_hi, log_lo);
-    else
-        hipLaunchKernelGGL((k_bitrev_scale_small<Fr>), dim3(grid_for(n), nvec), dim3(256), 0, st, dst, src, log_m, scale, c_lo, c_hi, log_lo);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 
-// scalar-dependent half of the MSM: digits, histogram, scan, scatter.  Scratch layout (must match msm_sort_scratch_bytes):
-// digits | sorted | counts | cursors | offsets.   evs (optional, 2 events) bracket the stage.
-struct MsmSortPtrs { const uint32_t* sorted; const uint32_t* offsets; const uint32_t* counts; uint32_t cap; const uint32_t* overflow; };   // cap = 0: dense list
+// scalar-dependent half of the MSM: digits, histogram, scan, scatter.  Scratch layout and size: msm_sort_scratch_bytes (launchers.hpp).
+// evs (optional, 2 events) bracket the stage.
 inline bool msm_sort_use_partition(size_t n, int c, int nwin, int shared) {
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
     const size_t nregions = (nbuckets + ((size_t)1 << PART_REGION_LOG) - 1) >> PART_REGION_LOG;
     return (size_t)nwin * n >= ((size_t)1 << 21) && nregions >= 8 && nregions <= PART_MAX_REGIONS;
-}
-inline size_t msm_sort_scratch_bytes(size_t n, int c, int nwin) {   // sized for the per-window bucket sets (the shared-set mode needs less)
-    const size_t nbuckets = (size_t)nwin << (c - 1);
-    const size_t entries = (size_t)nwin * n, ntiles = (entries + PART_TILE - 1) / PART_TILE;
-    return 2 * align_up(entries * 4) + 3 * align_up(nbuckets * 4) + align_up(((nbuckets + SCAN_TILE - 1) / SCAN_TILE) * 4) +
-           align_up(entries * 8) + 2 * align_up(PART_MAX_REGIONS * 4) + 256;       // partition path: items + region totals/cursors + item count
 }
 template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, char* scratch, MsmSortPtrs* out, hipEvent_t* evs) {
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
@@ -283,11 +255,7 @@ template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, siz
     out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = 0; out->overflow = nullptr;
     return 0;
 }
-// optimistic one-pass variant: scratch layout  sorted[nbuckets * cap] | counts | offsets | tile sums | overflow flag
-inline size_t msm_sort_direct_scratch_bytes(size_t n, int c, int nwin, int shared, uint32_t cap) {
-    const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
-    return align_up(nbuckets * cap * 4) + 2 * align_up(nbuckets * 4) + align_up(((nbuckets + SCAN_TILE - 1) / SCAN_TILE) * 4) + 256;
-}
+// optimistic one-pass variant (scratch: msm_sort_direct_scratch_bytes)
 template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, uint32_t cap, char* scratch, MsmSortPtrs* out, hipEvent_t* evs) {
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
     size_t off = 0;
@@ -313,37 +281,36 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
 
 }  // namespace cg
 
+// explicit instantiations, typed by the declarations of launchers.hpp: a definition above that differs from its declaration is a
+// second overload, and the instantiation below then fails to compile
 #define CG_INSTANTIATE_FR(Fr)                                                                                              \
     namespace cg {                                                                                                         \
-    template int launch_vec_binary<Fr>(hipStream_t, int, Fr*, const Fr*, const Fr*, size_t);                               \
-    template int launch_rep3_mul_local<Fr>(hipStream_t, Fr*, const Fr*, const Fr*, const Fr*, const Fr*, const Fr*, size_t); \
-    template int launch_distribute_powers<Fr>(hipStream_t, Fr*, size_t, const Fr*, const Fr*, int);                        \
-    template int launch_vec_count_noncanonical<Fr>(hipStream_t, const Fr*, size_t, unsigned long long*);                   \
-    template int launch_vec_fill<Fr>(hipStream_t, Fr*, size_t, const Fr&);                                                 \
-    template int launch_vec_gather_idx<Fr>(hipStream_t, Fr*, const Fr*, const uint32_t*, size_t, uint32_t);                \
-    template int launch_vec_affine<Fr>(hipStream_t, Fr*, const Fr*, size_t, const Fr&, const Fr&);                         \
-    template int launch_vec_gather_strided<Fr>(hipStream_t, Fr*, const Fr*, size_t, size_t, size_t);                       \
-    template int launch_vec_lincomb<Fr>(hipStream_t, Fr*, long long, long long, size_t, const LincombArgs<Fr>&);           \
-    template int launch_shamir_share<Fr>(hipStream_t, const Fr*, const Fr*, long long, long long, size_t, int, const ShareOuts<Fr>&, long long, long long); \
-    template int launch_plonk_r2_factors<Fr>(hipStream_t, const PlonkR2Args<Fr>&, size_t);                                  \
-    template int launch_prefix_scan<Fr>(hipStream_t, int, Fr*, const Fr*, size_t, Fr*);                                    \
-    template int launch_vec_inverse<Fr>(hipStream_t, Fr*, const Fr*, size_t);                                              \
-    template int launch_plonk_additions<Fr>(hipStream_t, const uint32_t*, size_t, const uint32_t*, const Fr*, const Fr*, uint32_t, int, Fr*, Fr*, size_t); \
-    template int launch_plonk_r3_blind<Fr>(hipStream_t, const PlonkBlindArgs<Fr>&, size_t);                                 \
-    template int launch_plonk_r3_perm<Fr>(hipStream_t, const PlonkPermArgs<Fr>&, size_t);                                   \
-    template int launch_plonk_r3_gate<Fr>(hipStream_t, const PlonkGateArgs<Fr>&, size_t);                                   \
-    template int launch_plonk_mul4_tail<Fr>(hipStream_t, const PlonkMul4Args<Fr>&, size_t);                                 \
-    template int launch_plonk_r3_t<Fr>(hipStream_t, const PlonkTArgs<Fr>&, size_t);                                         \
-    template int launch_plonk_r3_divide<Fr>(hipStream_t, const PlonkDivArgs<Fr>&, size_t);                                  \
-    template int launch_spmv_csr<Fr>(hipStream_t, const uint32_t*, const uint32_t*, const Fr*, size_t, const Fr*, uint32_t, int, const Fr*, const Fr*, Fr*, Fr*); \
-    template int launch_build_twiddles<Fr>(hipStream_t, Fr*, size_t, int, const Fr*, const Fr*, int);                      \
-    template int launch_ntt_dif_pass<Fr>(hipStream_t, NttVecs, NttVecs, int, size_t, int, int, int, int, const Fr*);                \
-    template int launch_build_twiddles_lazy<Fr>(hipStream_t, void*, size_t, int, const Fr*, const Fr*, int, const Fr&);             \
-    template int launch_ntt_ct_pass<Fr>(hipStream_t, bool, NttVecs, NttVecs, int, size_t, int, int, int, int, const void*);         \
-    template int launch_build_twiddles_lazy_natural<Fr>(hipStream_t, void*, size_t, const Fr*, const Fr*, int, const Fr&);          \
-    template int launch_ntt_dit_pass<Fr>(hipStream_t, bool, bool, NttVecs, NttVecs, int, size_t, int, int, int, int, const void*, const Fr*, const Fr*, int, const Fr&); \
-    template int launch_bitrev_finish_lazy<Fr>(hipStream_t, NttVecs, NttVecs, int, size_t, int, const Fr*, const Fr*, const Fr*, int); \
-    template int launch_bitrev_scale<Fr>(hipStream_t, NttVecs, NttVecs, int, size_t, int, const Fr*, const Fr*, const Fr*, int); \
-    template int msm_sort_launch<Fr>(hipStream_t, const Fr*, size_t, int, int, int, char*, MsmSortPtrs*, hipEvent_t*);          \
-    template int msm_sort_direct_launch<Fr>(hipStream_t, const Fr*, size_t, int, int, int, uint32_t, char*, MsmSortPtrs*, hipEvent_t*); \
+    template decltype(launch_vec_binary<Fr>) launch_vec_binary<Fr>;                                                        \
+    template decltype(launch_rep3_mul_local<Fr>) launch_rep3_mul_local<Fr>;                                                \
+    template decltype(launch_distribute_powers<Fr>) launch_distribute_powers<Fr>;                                          \
+    template decltype(launch_vec_count_noncanonical<Fr>) launch_vec_count_noncanonical<Fr>;                                \
+    template decltype(launch_vec_fill<Fr>) launch_vec_fill<Fr>;                                                            \
+    template decltype(launch_vec_gather_idx<Fr>) launch_vec_gather_idx<Fr>;                                                \
+    template decltype(launch_vec_affine<Fr>) launch_vec_affine<Fr>;                                                        \
+    template decltype(launch_vec_gather_strided<Fr>) launch_vec_gather_strided<Fr>;                                        \
+    template decltype(launch_vec_lincomb<Fr>) launch_vec_lincomb<Fr>;                                                      \
+    template decltype(launch_shamir_share<Fr>) launch_shamir_share<Fr>;                                                    \
+    template decltype(launch_plonk_r2_factors<Fr>) launch_plonk_r2_factors<Fr>;                                            \
+    template decltype(launch_prefix_scan<Fr>) launch_prefix_scan<Fr>;                                                      \
+    template decltype(launch_vec_inverse<Fr>) launch_vec_inverse<Fr>;                                                      \
+    template decltype(launch_plonk_additions<Fr>) launch_plonk_additions<Fr>;                                              \
+    template decltype(launch_plonk_r3_blind<Fr>) launch_plonk_r3_blind<Fr>;                                                \
+    template decltype(launch_plonk_r3_perm<Fr>) launch_plonk_r3_perm<Fr>;                                                  \
+    template decltype(launch_plonk_r3_gate<Fr>) launch_plonk_r3_gate<Fr>;                                                  \
+    template decltype(launch_plonk_mul4_tail<Fr>) launch_plonk_mul4_tail<Fr>;                                              \
+    template decltype(launch_plonk_r3_t<Fr>) launch_plonk_r3_t<Fr>;                                                        \
+    template decltype(launch_plonk_r3_divide<Fr>) launch_plonk_r3_divide<Fr>;                                              \
+    template decltype(launch_spmv_csr<Fr>) launch_spmv_csr<Fr>;                                                            \
+    template decltype(launch_build_twiddles_lazy<Fr>) launch_build_twiddles_lazy<Fr>;                                      \
+    template decltype(launch_ntt_ct_pass<Fr>) launch_ntt_ct_pass<Fr>;                                                      \
+    template decltype(launch_build_twiddles_lazy_natural<Fr>) launch_build_twiddles_lazy_natural<Fr>;                      \
+    template decltype(launch_ntt_dit_pass<Fr>) launch_ntt_dit_pass<Fr>;                                                    \
+    template decltype(launch_bitrev_finish_lazy<Fr>) launch_bitrev_finish_lazy<Fr>;                                        \
+    template decltype(msm_sort_launch<Fr>) msm_sort_launch<Fr>;                                                            \
+    template decltype(msm_sort_direct_launch<Fr>) msm_sort_direct_launch<Fr>;                                              \
     }

@@ -3,7 +3,7 @@
 // The scalar-dependent half (digits + counting sort) is in fr_impl.hpp and is shared between MSMs over the same scalars.
 #pragma once
 #include <cstdlib>
-#include "common.hpp"
+#include "launchers.hpp"
 #include "msm_kernels.hpp"
 
 namespace cg {
@@ -79,7 +79,7 @@ int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_
     if (one_fill) HIPCHK(hipMemsetAsync(S.buckets[0], 0, (size_t)(nsets - 1) * (size_t)stride + g.nbuckets * sizeof(B), st));
     else for (int i = 0; i < nsets; i++) HIPCHK(hipMemsetAsync(S.buckets[i], 0, g.nbuckets * sizeof(B), st));
     if (evs) HIPCHK(hipEventRecord(evs[0], st));
-    auto launch_acc = [&](auto kern, int T, size_t lds) -> int {                         // one set per launch (padded lists, CG_ACC_VARIANT=0)
+    auto launch_acc = [&](auto kern, int T, size_t lds) -> int {                         // the padded lists of a forced scatter capacity: one set per launch
         if (lds > 0) { if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc; }   // once per (kernel, device), not per launch
         for (int i = 0; i < nsets; i++)
             hipLaunchKernelGGL(kern, dim3((g.nchunks + T - 1) / T), dim3(T), lds, st, S.bases[i], S.sorted[i], S.offsets[i], S.counts[i],
@@ -89,14 +89,6 @@ int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_
     // accumulator policy per coordinate field (lazy limbs everywhere: 9 x 29 bits for BN254, 14 x 28 bits for BLS12-381 Fq):
     //   G1 (Fq)    accumulator in VGPRs, 256-lane workgroups
     //   G2 (Fq2)   accumulator in LDS (72 / 112 dwords per lane), 128-lane workgroups
-    int rc_acc;
-    // Compact lists (cap == 0) of the lazy-limb fields run the software-pipelined kernel.  CG_ACC_VARIANT (tuning knob, read per
-    // call; scripts/acc_variants.py): 0 = k_msm_accumulate, 1 = pipelined + L2 warm-up of the next record, 2 = pipelined + next
-    // record in registers (one wave per SIMD less), 3 / unset = pipelined boundary reads + index list read 16 bytes at a time (the default:
-    // the record prefetches measured no faster, the launch is bound by vector issue and not by the latency of the gather),
-    // 10 = 4-byte index reads two iterations ahead
-    const char* var_s = tune_env("CG_ACC_VARIANT");
-    const int variant = var_s ? atoi(var_s) : 3;
     // CG_OPT_MSM_G2_SLICES: the G2 accumulation goes one chip-load of workgroups at a time: its workgroups hold 147 of the CU's 160 KB
     // of LDS, so nothing that needs LDS (an NTT pass: 72 KB) can start while the launch lasts — measured: a high-priority NTT pass
     // waited 11 ms, the whole launch.  Between the slices the chip drains and the waiting kernels go first; ~2 ms per launch when nothing waits.
@@ -111,26 +103,11 @@ int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_
     constexpr bool g2 = IsFp2<F>::value;
     constexpr int MINW1 = sizeof(F) == 32 ? 3 : 2;            // G1 waves per SIMD the register budget is set for (BN254: 167 VGPRs; BLS12-381: 14-limb values)
     const size_t lds2 = g2 ? (size_t)128 * 4 * sizeof(typename LazyOf<F>::type) : 0;
-    if (variant && cap == 0) {
-        if constexpr (!g2) {
-            if (variant == 1) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 1>, 256, 256 * 4);
-            else if (variant == 2) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1 - 1, 2>, 256, 0);
-            else if (variant == 10) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0>, 256, 0);
-#ifdef CG_ACC_DEBUG_VARIANTS   // timing experiments with wrong results (scripts/acc_variants.py): where the launch spends its time
-            else if (variant == 4) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0, 1>, 256, 0);
-            else if (variant == 5) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0, 2>, 256, 0);
-            else if (variant == 6) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0, 3>, 256, 0);
-            else if (variant == 7) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0, 7>, 256, 0);
-            else if (variant == 8) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0, 4>, 256, 0);
-            else if (variant == 9) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 0, 8>, 256, 0);
-#endif
-            else rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1, 3>, 256, 0);
-        } else {
-            if (variant == 1) rc_acc = launch_pf(k_msm_accumulate_pf<F, LdsAcc29<F>, 128, 1, 1>, 128, lds2 + 128 * 4);
-            else if (variant == 2) rc_acc = launch_pf(k_msm_accumulate_pf<F, LdsAcc29<F>, 128, 1, 2>, 128, lds2);
-            else if (variant == 10) rc_acc = launch_pf(k_msm_accumulate_pf<F, LdsAcc29<F>, 128, 1, 0>, 128, lds2);
-            else rc_acc = launch_pf(k_msm_accumulate_pf<F, LdsAcc29<F>, 128, 1, 3>, 128, lds2);   // (256-lane workgroups, two per CU, were A/B'd in round 4: no gain beside a chain, +2 ms alone)
-        }
+    // compact lists (cap == 0) run the software-pipelined kernel, padded ones (cg_msm_set_scatter_capacity) the plain one
+    int rc_acc;
+    if (cap == 0) {
+        if constexpr (!g2) rc_acc = launch_pf(k_msm_accumulate_pf<F, RegAcc29<F>, 256, MINW1>, 256, 0);
+        else rc_acc = launch_pf(k_msm_accumulate_pf<F, LdsAcc29<F>, 128, 1>, 128, lds2);   // (256-lane workgroups, two per CU, were A/B'd in round 4: no gain beside a chain, +2 ms alone)
     } else if constexpr (!g2) rc_acc = launch_acc(k_msm_accumulate<F, RegAcc29<F>, 256>, 256, 0);
     else rc_acc = launch_acc(k_msm_accumulate<F, LdsAcc29<F>, 128>, 128, lds2);
     if (rc_acc) return rc_acc;
@@ -280,17 +257,18 @@ int fixed_base_mul_launch(hipStream_t st, const Affine<F>& g, const Fr* d_scalar
 
 }  // namespace cg
 
+// explicit instantiations, typed by the declarations of launchers.hpp (see fr_impl.hpp)
 #define CG_INSTANTIATE_MSM(F, Fr)                                                                                          \
     namespace cg {                                                                                                         \
-    template int msm_accumulate_batch<F>(hipStream_t, const MsmAccSet*, int, size_t, int, int, bool, uint32_t, hipEvent_t*, uint32_t, bool); \
-    template int msm_reduce_batch<F>(hipStream_t, const MsmRedSet*, int, size_t, int, int, bool, uint32_t, hipEvent_t*, int, hipEvent_t*, uint32_t); \
-    template size_t msm_acc_scratch_bytes<F>(size_t, int, int, bool, uint32_t);                                                      \
-    template int precompute_window_launch<F>(hipStream_t, const Affine<F>*, Affine<F>*, size_t, int);                      \
-    template int check_on_curve_launch<F>(hipStream_t, const Affine<F>*, size_t, const F&, unsigned long long*);           \
-    template int check_subgroup_launch<F, Fr>(hipStream_t, const Affine<F>*, size_t, unsigned long long*);                 \
-    template int check_subgroup_fast_launch<F>(hipStream_t, const Affine<F>*, size_t, const FastSubgroup<F>&, unsigned long long*); \
-    template int pack_bases_launch<F>(hipStream_t, const uint8_t*, size_t, size_t, long, Affine<F>*);                      \
-    template int gather_points_launch<F>(hipStream_t, Affine<F>*, const Affine<F>*, const uint32_t*, size_t);              \
-    template int synth_points_launch<F>(hipStream_t, const XYZZ<F>*, const XYZZ<F>*, int, size_t, Affine<F>*);             \
-    template int fixed_base_mul_launch<F, Fr>(hipStream_t, const Affine<F>&, const Fr*, size_t, Affine<F>*, Affine<F>*);   \
+    template decltype(msm_accumulate_batch<F>) msm_accumulate_batch<F>;                                                    \
+    template decltype(msm_reduce_batch<F>) msm_reduce_batch<F>;                                                            \
+    template decltype(msm_acc_scratch_bytes<F>) msm_acc_scratch_bytes<F>;                                                  \
+    template decltype(precompute_window_launch<F>) precompute_window_launch<F>;                                            \
+    template decltype(check_on_curve_launch<F>) check_on_curve_launch<F>;                                                  \
+    template decltype(check_subgroup_launch<F, Fr>) check_subgroup_launch<F, Fr>;                                          \
+    template decltype(check_subgroup_fast_launch<F>) check_subgroup_fast_launch<F>;                                        \
+    template decltype(pack_bases_launch<F>) pack_bases_launch<F>;                                                          \
+    template decltype(gather_points_launch<F>) gather_points_launch<F>;                                                    \
+    template decltype(synth_points_launch<F>) synth_points_launch<F>;                                                      \
+    template decltype(fixed_base_mul_launch<F, Fr>) fixed_base_mul_launch<F, Fr>;                                          \
     }

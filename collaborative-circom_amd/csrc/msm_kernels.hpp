@@ -49,7 +49,6 @@ __device__ __forceinline__ void st_struct(A* p, const A& r) {
 template <class F>
 struct RegAcc {
     typedef uint4 LdsT;
-    static constexpr bool USES_LDS = false;
     XYZZ<F> v;
     bool inf;
     __device__ __forceinline__ void init(uint4*, int, int) { inf = true; }
@@ -59,8 +58,6 @@ struct RegAcc {
 template <class F>
 struct LdsAcc {
     typedef uint4 LdsT;
-    static constexpr bool USES_LDS = true;
-    static constexpr size_t LDS_BYTES_PER_LANE = sizeof(XYZZ<F>);
     static constexpr int Q = sizeof(F) / 16;          // 16-byte quads per coordinate
     uint4* base; int stride;                           // quad e of this lane at base[e * stride]
     bool inf;
@@ -107,9 +104,6 @@ __device__ __forceinline__ void acc_flush(Acc& acc, XYZZ<F>* dst) {
 // column accumulation (18 signed products + 9 reduction products per column: < 27 * 2^58 < 2^63) followed by ONE reduction,
 // i.e. the same 486 multiplies as Karatsuba but no pre/post additions and 2 instead of 3 reductions.
 // Bounds (d = 0.45, units of p, per component): products in (-d, 1+d); X in (-4.8, 2.8); Y in (-1.9, 1.9); P in (-3.3, 6.3).
-#ifndef CG_L29X2_INLINE
-#define CG_L29X2_INLINE __forceinline__
-#endif
 template <class F2>
 struct L29x2 {
     typedef typename F2::Base F;
@@ -136,10 +130,10 @@ struct L29x2 {
         }
         return L::upper_half(T);
     }
-    static __device__ CG_L29X2_INLINE L29x2 mul(const L29x2& a, const L29x2& b) {
+    static __device__ __forceinline__ L29x2 mul(const L29x2& a, const L29x2& b) {
         return {mul2<-1>(a.c0, b.c0, a.c1, b.c1), mul2<+1>(a.c0, b.c1, a.c1, b.c0)};
     }
-    static __device__ CG_L29X2_INLINE L29x2 sqr(const L29x2& a) {
+    static __device__ __forceinline__ L29x2 sqr(const L29x2& a) {
         L s = (a.c0 + a.c1).norm(), d = (a.c0 - a.c1).norm();     // limb magnitude back to 2^29 before multiplying
         return {L::mul(s, d), L::mul(a.c0.dbl(), a.c1)};
     }
@@ -173,7 +167,6 @@ template <class F>
 struct RegAcc29 {
     typedef uint32_t LdsT;
     typedef typename LazyOf<F>::type L;
-    static constexpr bool USES_LDS = false;
     L c[4];
     bool inf;
     __device__ __forceinline__ void init(uint32_t*, int, int) { inf = true; }
@@ -184,8 +177,6 @@ template <class F>
 struct LdsAcc29 {
     typedef uint32_t LdsT;
     typedef typename LazyOf<F>::type L;
-    static constexpr bool USES_LDS = true;
-    static constexpr size_t LDS_BYTES_PER_LANE = 4 * sizeof(L);
     static constexpr int W = sizeof(L) / 4;               // dwords per coordinate
     uint32_t* base; int stride; bool inf;
     __device__ __forceinline__ void init(uint32_t* lds, int tid, int nthreads) { base = lds + tid; stride = nthreads; inf = true; }
@@ -384,9 +375,7 @@ __device__ __forceinline__ void acc_madd_lazy(Acc& acc, const F& x2f, const F& y
         acc.set(0, L::unpack_small(x2f)); acc.set(1, negate ? ys.neg().norm() : ys); acc.set(2, one); acc.set(3, one); acc.inf = false;
         return;
     }
-#if !defined(CG_ACC_ROWS)                        // round 6 default: products by columns (-DCG_ACC_ROWS: the row form of rounds 2-5, for A/B runs)
-    if constexpr (HasColEngine<L>::value) { acc_madd_lazy_cols<F>(acc, x2f, y2f, x2, y2, negate); return; }
-#endif
+    if constexpr (HasColEngine<L>::value) { acc_madd_lazy_cols<F>(acc, x2f, y2f, x2, y2, negate); return; }   // products by columns; the row form below serves the rest (BLS12-381 G2)
     L P = L::mul(x2, acc.get(2)) - acc.get(0);
     L R = L::mul(y2, acc.get(3)) - acc.get(1);
     if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) {   // same x: doubling or cancellation (rare)
@@ -484,11 +473,13 @@ __global__ void __launch_bounds__(THREADS, MINW) k_msm_accumulate(const Affine<F
 // spends the cycles it does not issue in (SQ_WAIT_ANY 19 % of wave time at 3 waves per SIMD): three dependent memory round trips
 // per entry — sorted[pos] (L2), then the 64/128-byte gather bases[...] (HBM, random), and on nearly every second iteration of a
 // WAVE (some lane of 64 crosses a bucket boundary) counts[b] / offsets[b] of the next bucket.  Here
-//   * the sorted entries are read two iterations ahead (e0 current, e1 next, e2 in flight),
-//   * the end of the NEXT bucket (offsets[b + 2]) is read when a bucket is entered, so a boundary costs no round trip,
-//   * PF == 1: the record of the next entry is pulled into L2 while the current addition runs: one global_load_lds_dword per
-//     64 bytes into a junk LDS slot (no VGPR destination, nothing to wait for), issued after the current record has arrived;
-//   * PF == 2: the next record itself is loaded into registers before the current addition (for a 2-wave-per-SIMD build).
+//   * the index list is read 16 bytes per lane every fourth iteration instead of 4 bytes every iteration: a lane's entries are
+//     consecutive, but 64 lanes x 4 bytes touch 64 cache lines per load and each line comes back from L2 — or, evicted by the
+//     gathers streaming through, from HBM — 32 times (1 GB of the 4.8 GB a 2^22 launch reads, r02_pmc_traffic.json);
+//   * the end of the NEXT bucket (offsets[b + 2]) is read when a bucket is entered, so a boundary costs no round trip;
+//   * a launch may cover a slice of the chunks (first_chunk), see msm_accumulate_batch.
+// Prefetching the next entry's record (into L2 through a junk LDS slot, or into registers) was tried and measured no faster: the
+// launch is bound by vector issue, not by the latency of the gather (docs/history/).
 // Up to ACC_MAX_SETS accumulations of ONE launch geometry in one launch (blockIdx.y = set): the tables and share components of a small
 // MSM call (2^16 constraints: a launch of 256 workgroups leaves three quarters of the chip idle and lasts as long as one lane's chain
 // of additions, so eight launches in a row cost eight such chains; side by side they cost one).  Large calls pass one set.
@@ -499,18 +490,15 @@ struct AccSets {
     typename BucketOf<F>::type* buckets[ACC_MAX_SETS]; typename BucketOf<F>::type* cont[ACC_MAX_SETS]; uint32_t* cont_bucket[ACC_MAX_SETS];
     uint32_t table_stride[ACC_MAX_SETS]; uint32_t may_have_inf[ACC_MAX_SETS];
 };
-template <class Acc, int THREADS> __host__ __device__ constexpr size_t acc_lds_bytes() {
-    if constexpr (Acc::USES_LDS) return (size_t)THREADS * Acc::LDS_BYTES_PER_LANE; else return 0;
-}
-template <class F, class Acc, int THREADS, int MINW, int PF, int DBG = 0>
+template <class F, class Acc, int THREADS, int MINW>
 __global__ void __launch_bounds__(THREADS, MINW) k_msm_accumulate_pf(const AccSets<F> S, uint32_t nbuckets, uint32_t chunk_len, uint32_t nchunks, uint32_t first_chunk) {
     const Affine<F>* __restrict__ bases = S.bases[blockIdx.y]; const uint32_t* __restrict__ sorted = S.sorted[blockIdx.y];
     const uint32_t* __restrict__ offsets = S.offsets[blockIdx.y]; const uint32_t* __restrict__ counts = S.counts[blockIdx.y];
     typename BucketOf<F>::type* __restrict__ buckets = S.buckets[blockIdx.y]; typename BucketOf<F>::type* __restrict__ cont = S.cont[blockIdx.y];
     uint32_t* __restrict__ cont_bucket = S.cont_bucket[blockIdx.y];
     const uint32_t table_stride = S.table_stride[blockIdx.y], may_have_inf = S.may_have_inf[blockIdx.y];
-    extern __shared__ uint4 acc_lds[];        // [accumulators (LDS policies)] [PF == 1: THREADS junk dwords, see PF_JUNK_OFFSET]
-    const uint32_t q = first_chunk + blockIdx.x * THREADS + threadIdx.x;   // first_chunk: a launch may cover a slice of the chunks (msm_accumulate_reduce)
+    extern __shared__ uint4 acc_lds[];        // accumulators (LDS policies)
+    const uint32_t q = first_chunk + blockIdx.x * THREADS + threadIdx.x;
     if (q >= nchunks) return;
     const uint32_t total = offsets[nbuckets - 1] + counts[nbuckets - 1];
     uint32_t pos = q * chunk_len;
@@ -525,60 +513,24 @@ __global__ void __launch_bounds__(THREADS, MINW) k_msm_accumulate_pf(const AccSe
     cont_bucket[q] = continuation ? b : 0xffffffffu;
     Acc acc;
     acc.init(reinterpret_cast<typename Acc::LdsT*>(acc_lds), threadIdx.x, THREADS);
-    // DBG (timing experiments only, results are wrong): 1 = cache-resident gather addresses, 2 = bucket boundaries ignored
-    auto at_of = [&](uint32_t e) -> size_t {
-        if constexpr (DBG & 1) return (size_t)(threadIdx.x + 256u * (e & 63u));
-        if constexpr (DBG & 8) return (size_t)((e * 2654435761u) >> 12);                   // random over 2^20 records (64 MB: few pages, no cache reuse)
-        return table_stride ? (size_t)((e >> 24) & 0x7fu) * table_stride + (e & 0xffffffu) : (size_t)(e & 0x7fffffffu);
-    };
-    auto entry = [&](uint32_t at) -> uint32_t { if constexpr (DBG & 4) return at * 2654435761u; else return sorted[at]; };   // DBG 4: no index loads
-    uint32_t e0 = 0, e1 = 0;
-    // PF == 3: the index list is read 16 bytes per lane every fourth iteration instead of 4 bytes every iteration:
-    // a lane's entries are consecutive, but 64 lanes x 4 bytes touch 64 cache lines per load and each line comes back from L2 — or,
-    // evicted by the gathers streaming through, from HBM — 32 times (1 GB of the 4.8 GB a 2^22 launch reads, r02_pmc_traffic.json)
-    uint4 cur = make_uint4(0, 0, 0, 0);
     auto quad = [&](uint32_t at4) -> uint4 { return *reinterpret_cast<const uint4*>(sorted + at4); };    // reads past `end` stay inside the arena and are never used
-    if constexpr (PF == 3) {
-        cur = quad(pos & ~3u);
-        for (uint32_t k = 0; k < (pos & 3u); k++) { cur.x = cur.y; cur.y = cur.z; cur.z = cur.w; }
-    } else {
-        e0 = entry(pos);
-        e1 = pos + 1 < end ? entry(pos + 1) : e0;
-    }
-    Affine<F> pn;
-    Affine<F> psyn;                                                                  // DBG 4: operands from registers, no gather
-    if constexpr (DBG & 4) { uint32_t* w = reinterpret_cast<uint32_t*>(&psyn); for (int i = 0; i < (int)(sizeof(psyn) / 4); i++) w[i] = (threadIdx.x * 2654435761u + i * 40503u) & 0x0fffffffu; }
-    if constexpr (PF == 2) pn = ld_struct(bases + at_of(e0));
+    uint4 cur = quad(pos & ~3u);                             // cur.x is the current entry
+    for (uint32_t k = 0; k < (pos & 3u); k++) { cur.x = cur.y; cur.y = cur.z; cur.z = cur.w; }
     while (pos < end) {
-        if (!(DBG & 2) && pos == bend) {                     // finished bucket b inside this chunk
+        if (pos == bend) {                                   // finished bucket b inside this chunk
             if (continuation) { acc_store<F>(acc, cont + q); continuation = false; } else acc_store<F>(acc, buckets + b);
             b++; bend = bend_next; bend_next = end_of(b + 1);
             while (bend == pos) { b++; bend = bend_next; bend_next = end_of(b + 1); }      // empty buckets (rare)
         }
-        // load order matters: vmcnt counts in issue order, so the index read two iterations ahead is issued AFTER the record
-        // loads — the wait for the current record then leaves it (and, PF == 2, the next record) in flight
-        Affine<F> p;
-        if constexpr (DBG & 4) { uint32_t* w = reinterpret_cast<uint32_t*>(&psyn); w[0] += 0x9e3779b9u; w[9] ^= w[0]; p = psyn; }
-        else if constexpr (PF == 2) { p = pn; pn = ld_struct(bases + at_of(e1)); }
-        else { if constexpr (PF == 3) e0 = cur.x; p = ld_struct(bases + at_of(e0)); }
-        uint32_t e2 = 0;
-        if constexpr (PF == 3) {
-            cur.x = cur.y; cur.y = cur.z; cur.z = cur.w;
-            if (((pos + 1) & 3u) == 0 && pos + 1 < end) cur = quad(pos + 1);   // issued behind the record loads: it arrives during this addition
-        } else e2 = pos + 2 < end ? entry(pos + 2) : e1;
-        if constexpr (PF == 1) {
-            // after the last quad of p has arrived (the empty asm makes the address depend on it), so that the wait for p is not
-            // extended to this load
-            const uint32_t* w = reinterpret_cast<const uint32_t*>(&p);
-            uintptr_t a = reinterpret_cast<uintptr_t>(bases + at_of(e1));
-            asm volatile("" : "+v"(a) : "v"(w[0]), "v"(w[sizeof(Affine<F>) / 4 - 1]), "v"(w[sizeof(Affine<F>) / 8]), "v"(w[sizeof(Affine<F>) / 8 - 1]));
-            _Pragma("unroll") for (int k = 0; k < (int)(sizeof(Affine<F>) / 32); k++)
-                __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint32_t*>(a) + 8 * k,
-                                                 (__attribute__((address_space(3))) uint32_t*)(reinterpret_cast<char*>(acc_lds) + acc_lds_bytes<Acc, THREADS>()), 4, 0, 0);
-        }
-        const bool neg = (e0 >> 31) != 0;
+        // load order matters: vmcnt counts in issue order, so the next index quad is issued AFTER the record loads — the wait
+        // for the current record then leaves it in flight, and it arrives during this addition
+        const uint32_t e = cur.x;
+        const size_t at = table_stride ? (size_t)((e >> 24) & 0x7fu) * table_stride + (e & 0xffffffu) : (size_t)(e & 0x7fffffffu);
+        Affine<F> p = ld_struct(bases + at);
+        cur.x = cur.y; cur.y = cur.z; cur.z = cur.w;
+        if (((pos + 1) & 3u) == 0 && pos + 1 < end) cur = quad(pos + 1);
+        const bool neg = (e >> 31) != 0;
         pos++;
-        if constexpr (PF != 3) { e0 = e1; e1 = e2; }
         if (may_have_inf && p.is_inf()) continue;
         acc_madd(acc, p.x, p.y, neg);
     }

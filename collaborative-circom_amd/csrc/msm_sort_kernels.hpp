@@ -4,6 +4,7 @@
 // co-groth16 the aux-witness shares drive l_query, a_query, b_g1_query and b_g2_query (groth16.rs:251,267,284,298).
 #pragma once
 #include "field.hpp"
+#include "launchers.hpp"   // SCAN_TILE, PART_*: the tile sizes the scratch sizes are computed from
 #include "vec_kernels.hpp"
 
 namespace cg {
@@ -32,8 +33,7 @@ __global__ void __launch_bounds__(256) k_msm_digits(const Fr* __restrict__ scala
     }
 }
 
-// exclusive prefix sum of `total` counters in three launches: per-tile sums, scan of the tile sums, per-tile scan + base.
-constexpr int SCAN_TILE = 2048;     // counters per workgroup (256 lanes x 8)
+// exclusive prefix sum of `total` counters in three launches: per-tile sums, scan of the tile sums, per-tile scan + base (tiles of SCAN_TILE).
 static __global__ void __launch_bounds__(256) k_scan_tile_sums(const uint32_t* __restrict__ in, uint32_t* __restrict__ tile_sums, size_t total, uint32_t cap) {
     __shared__ uint32_t red[256];
     const size_t base = (size_t)blockIdx.x * SCAN_TILE;
@@ -155,9 +155,6 @@ __global__ void __launch_bounds__(1024) k_msm_sort_small(const Fr* __restrict__ 
 //   k_part_colscan  per-region totals -> region bases; per-(tile, region) offsets
 //   k_part_scatter  items[(bucket << 32) | payload] grouped by region (rank inside the tile via LDS atomics)
 //   k_items_hist / k_items_scatter   the counting sort proper, reading the region-grouped items
-constexpr int PART_TILE = 16384;
-constexpr int PART_REGION_LOG = 9;      // 512 buckets per region
-constexpr int PART_MAX_REGIONS = 4096;  // LDS histogram limit
 
 __device__ __forceinline__ bool part_decode(int32_t dig, size_t w, uint32_t i, uint32_t nb, int shared, uint32_t* bucket, uint32_t* payload) {
     if (dig == 0) return false;

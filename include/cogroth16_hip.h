@@ -175,8 +175,8 @@ int32_t cg_msm_scalars_after(cg_ctx* ctx, int32_t component, cg_ctx* owner, int3
  * Everything else that was an environment variable until round 5 is now one of:
  *   * a per-context option (cg_ctx_set_option, table below) or a process-wide option (cg_set_option, table further down);
  *   * an A/B knob of the measurement scripts that exists ONLY in the planning build (make -C collaborative-circom_amd/csrc KNOBS=1 ->
- *     libcogroth16_hip_knobs.so, -DCG_DEBUG_KNOBS): CG_MSM_CHUNK, CG_MSM_CHUNK_MIN, CG_G2_CHUNK, CG_MSM_NO_ROUNDS, CG_ACC_VARIANT, CG_NO_BITSUM,
- *     CG_NO_GRID_REDUCE, CG_NTT_DIF, CG_NTT_NO_PAIR, CG_NTT_TILE, CG_BULK_CLASS, CG_NO_STREAM_PROBE, CG_NO_PIPE_MAP, the CG_MSM_* seeds of new contexts'
+ *     libcogroth16_hip_knobs.so, -DCG_DEBUG_KNOBS): CG_MSM_CHUNK, CG_MSM_CHUNK_MIN, CG_G2_CHUNK, CG_MSM_NO_ROUNDS, CG_NO_BITSUM,
+ *     CG_NO_GRID_REDUCE, CG_NTT_TILE, CG_BULK_CLASS, CG_NO_STREAM_PROBE, CG_NO_PIPE_MAP, the CG_MSM_* seeds of new contexts'
  *     option tables, and CG_DEBUG_NO_REDUCE (skips the bucket reductions: RESULTS ARE WRONG — what they cost a step).  The release library
  *     does not contain these names. */
 /* ---- per-context tuning (never changes results).  One table instead of process-wide environment variables: every option belongs to the

@@ -95,3 +95,30 @@ def test_nine_vectors_are_refused_and_left_unchanged(ctx, curve):
             np.testing.assert_array_equal(b.download((n, 4)), vs[i], err_msg=f"vector {i}")
     finally:
         ctx.free_many(d)
+
+
+def refused_and_unchanged(ctx, curve, calls, message):
+    """every call of `calls(d, n, w, g)` on eight lg-6 vectors raises `message`, and the buffers hold afterwards what they held before"""
+    lg = 6
+    n = 1 << lg
+    vs, w, g = vectors(curve, lg)
+    d = [ctx.to_device(v) for v in vs]
+    try:
+        for fn in calls(d, n, w, g):
+            with pytest.raises(cg.BackendError, match=message):
+                fn()
+        for i, b in enumerate(d):
+            np.testing.assert_array_equal(b.download((n, 4)), vs[i], err_msg=f"vector {i}")
+    finally:
+        ctx.free_many(d)
+
+
+@pytest.mark.parametrize("curve", [BN254, BLS12_381], ids=["bn254", "bls12_381"])
+def test_forward_transform_with_coset_gen_is_refused_and_leaves_the_vectors_unchanged(ctx, curve):
+    refused_and_unchanged(ctx, curve, lambda d, n, w, g: [lambda: ctx.ntt_dev(curve, d, n, w, coset_gen=g)], "coset_gen is only supported with inverse != 0")
+
+
+@pytest.mark.parametrize("curve", [BN254, BLS12_381], ids=["bn254", "bls12_381"])
+def test_length_48_is_refused_and_leaves_the_vectors_unchanged(ctx, curve):
+    refused_and_unchanged(ctx, curve, lambda d, n, w, g: [lambda: ctx.ntt_dev(curve, d, 48, w), lambda: ctx.ntt_dev(curve, d, 48, w, inverse=True, coset_gen=g),
+                                                          lambda: ctx.ntt_coset_pair_dev(curve, d, 48, w, g)], "NTT length must be a power of two")
