@@ -265,7 +265,9 @@ struct L29 {
         return upper_half(T);
     }
     __device__ __forceinline__ static XYZZ<F> dbl_affine(const F& x, const F& y) { return xyzz_dbl_affine(x, y); }
-    // small representative (0.5p .. 1.6p) of 1 in the 2^(NL W) domain: (2^SH R1)^2 / 2^(NL W) = 2^(NL W) (mod p), R1 = 2^(32N) mod p
+    // a representative of 1 in the 2^(NL W) domain: (2^SH R1)^2 / 2^(NL W) = 2^(NL W) (mod p), R1 = 2^(32N) mod p.  Small (0.5p .. 1.7p) for the 256-bit
+    // fields only: on BLS12-381 Fq 2^SH R1 = 216 p and the value lies in (18.5p, 19.6p) — accumulator coordinates are built with one_small() instead
+    // (no kernel calls this any more; it stays as the definition one_small() is checked against: tests/sanitize/lazy_bucket_main.cpp, check 2)
     __device__ __forceinline__ static L29 one() { const L29 o = unpack<SH>(F::one()); return mul(o, o); }
     // the same residue in [0, p) without a product (constant-folded: F::one() is a compile-time constant)
     __device__ __forceinline__ static L29 one_small() {

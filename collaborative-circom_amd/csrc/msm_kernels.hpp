@@ -309,7 +309,7 @@ __device__ __forceinline__ void acc_madd_lazy_cols(Acc& acc, const F& x2f, const
             XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
             acc.inf = d.is_inf();
             if (!acc.inf) {
-                const L one = L::one();
+                const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
                 constexpr int SH = LazyShift<L>::value;
                 acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
                 acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
@@ -343,7 +343,7 @@ __device__ __forceinline__ void acc_madd_lazy_cols(Acc& acc, const F& x2f, const
             XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
             acc.inf = d.is_inf();
             if (!acc.inf) {
-                const L one = L::one();
+                const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
                 constexpr int SH = LazyShift<L>::value;
                 acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
                 acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
@@ -383,7 +383,7 @@ __device__ __forceinline__ void acc_madd_lazy(Acc& acc, const F& x2f, const F& y
             XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
             acc.inf = d.is_inf();
             if (!acc.inf) {
-                const L one = L::one();
+                const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
                 constexpr int SH = LazyShift<L>::value;
                 acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
                 acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
