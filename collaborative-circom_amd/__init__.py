@@ -55,7 +55,7 @@ ABI_SYMBOLS = [
     "cg_ntt", "cg_ntt_dev", "cg_ntt_coset_pair_dev", "cg_chacha12_fr_rand_dev", "cg_chacha12_fr_rand_dev_begin", "cg_chacha12_fr_rand_dev_finish",
     "cg_host_alloc", "cg_host_free", "cg_host_is_pinned", "cg_dev_download_begin", "cg_dev_upload_begin", "cg_stream_mark", "cg_dev_download_begin_after", "cg_copy_wait", "cg_copy_fence",
     "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_shamir_share_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
-    "cg_spmv_csr_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
+    "cg_spmv_csr_dev", "cg_r1cs_check_dev", "cg_qap_columns_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
     "cg_plonk_additions_dev", "cg_plonk_r2_factors_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
@@ -545,6 +545,17 @@ class Context:
     def vec_prefix_sum(self, curve, out, src, n): _chk(load().cg_vec_prefix_sum_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
     def vec_inverse(self, curve, out, src, n): _chk(load().cg_vec_inverse_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
 
+    def r1cs_check(self, curve, mats, n_rows, witness, result, nnz_total=0, form=0):
+        """cg_r1cs_check_dev: mats = three (row_ptr, col, coeff) device triples (A, B, C); result = 16-byte device buffer (count, first failing row);
+        form 0 = chosen by size, 1 = a lane per row triple, 2 = a wave per row triple"""
+        _chk(load().cg_r1cs_check_dev(self.h, curve, _ptr_list([m[0] for m in mats]), _ptr_list([m[1] for m in mats]), _ptr_list([m[2] for m in mats]),
+                                      C.c_size_t(n_rows), C.c_size_t(nnz_total), int(form), _dp(witness), _dp(result)))
+
+    def qap_columns(self, curve, col_ptr, row, coeff, n_cols, lagrange, out, long_min=0):
+        """cg_qap_columns_dev: out[i] = sum over the entries of column i of coeff * lagrange[row] (column-major matrix); long_min = entries from
+        which the workgroup, not one lane, sums a column (0 = the library's default)"""
+        _chk(load().cg_qap_columns_dev(self.h, curve, _dp(col_ptr), _dp(row), _dp(coeff), C.c_size_t(n_cols), C.c_uint32(long_min), _dp(lagrange), _dp(out)))
+
     def spmv_csr(self, curve, row_ptr, col, coeff, n_rows, pub, n_inputs, party, wit_a, wit_b, out_a, out_b):
         _chk(load().cg_spmv_csr_dev(self.h, curve, _dp(row_ptr), _dp(col), _dp(coeff), C.c_size_t(n_rows), _dp(pub), C.c_uint32(n_inputs), int(party),
                                     _dp(wit_a), _dp(wit_b), _dp(out_a), _dp(out_b)))
@@ -868,6 +879,61 @@ def host_synth_plonk_circuit(curve, log_n, seed, zkey_path, wtns_path, n_public=
     polynomials' evaluations by the library's NTT on the GPU), written as a snarkjs-format Plonk .zkey + .wtns (bench / test tooling)"""
     _hchk(load_host().cgh_synth_plonk_circuit(int(device), curve, int(log_n), C.c_uint64(seed), C.c_uint32(n_public), C.c_uint32(n_additions),
                                               zkey_path.encode(), wtns_path.encode()))
+
+
+NO_ROW = (1 << 64) - 1
+
+
+class R1cs:
+    """an iden3 .r1cs file (cgh_r1cs_*): the three constraint matrices, the zkey coefficient section they determine, the witness check on the GPU"""
+
+    def __init__(self, curve, path):
+        h = C.c_void_p()
+        _hchk(load_host().cgh_r1cs_open(curve, path.encode(), C.byref(h)))
+        self.curve, self.h = curve, h
+        info = (C.c_size_t * 7)()
+        _hchk(load_host().cgh_r1cs_info(self.h, info))
+        self.info = dict(zip(("n_wires", "n_public", "n_constraints", "domain_size", "nnz_a", "nnz_b", "nnz_c"), [int(x) for x in info]))
+
+    def close(self):
+        if self.h: load_host().cgh_r1cs_close(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def coeff_section(self):
+        """section 4 of the Groth16 zkey of this circuit, as bytes (host only)"""
+        n = C.c_size_t(0)
+        _hchk(load_host().cgh_r1cs_coeff_section(self.h, None, C.c_size_t(0), C.byref(n)))
+        buf = (C.c_uint8 * n.value)()
+        _hchk(load_host().cgh_r1cs_coeff_section(self.h, buf, C.c_size_t(n.value), C.byref(n)))
+        return bytes(buf)
+
+    def check_witness(self, witness, device=0, form=0):
+        """(n_bad, first_bad) of the plain full witness (n_wires Montgomery elements): the number of constraints it violates and the smallest
+        such row, NO_ROW when it satisfies the circuit.  form: 0 = kernel form chosen by size, 1 = a lane per row, 2 = a wave per row."""
+        w = np.ascontiguousarray(witness, dtype=np.uint64).reshape(-1, 4)
+        if w.shape[0] != self.info["n_wires"]:
+            raise BackendError(f"cogroth16_host: a witness of {w.shape[0]} values for a circuit of {self.info['n_wires']} wires")
+        n_bad, first = C.c_uint64(0), C.c_uint64(0)
+        _hchk(load_host().cgh_r1cs_check_witness_form(int(device), self.h, int(form), _hp(w), C.byref(n_bad), C.byref(first)))
+        return int(n_bad.value), int(first.value)
+
+
+def setup_groth16(r1cs, seed, zkey_path, device=0):
+    """a snarkjs-format Groth16 .zkey for the circuit from seeded toxic waste (cgh_setup_groth16_dev), computed on the GPU.
+    DEVELOPMENT ONLY: whoever holds the seed can forge proofs for this key."""
+    _hchk(load_host().cgh_setup_groth16_dev(int(device), r1cs.h, C.c_uint64(seed), zkey_path.encode()))
+
+
+def setup_toxic(curve, seed):
+    """tau, alpha, beta, gamma, delta of setup_groth16 for a seed, Montgomery (5, 4)"""
+    out = np.zeros((5, 4), dtype=np.uint64)
+    _hchk(load_host().cgh_setup_toxic(curve, C.c_uint64(seed), _hp(out)))
+    return out
 
 
 def host_set_zkey_validation(on):

@@ -700,6 +700,33 @@ int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, c
     });
 }
 
+int32_t cg_r1cs_check_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff, size_t n_rows,
+                          size_t nnz_total, int32_t form, const void* d_witness, void* d_result) {
+    if (!ctx || !d_row_ptr || !d_col || !d_coeff || !d_witness || !d_result) return fail(CG_ERR_ARG, "null argument");
+    if (form < 0 || form > 2) return fail(CG_ERR_ARG, "cg_r1cs_check_dev: form must be 0 (chosen by size), 1 (lane per row) or 2 (wave per row)");
+    R1csMat m[3];
+    for (int i = 0; i < 3; i++) {
+        if (n_rows && !d_row_ptr[i]) return fail(CG_ERR_ARG, "null row pointers");
+        m[i] = R1csMat{d_row_ptr[i], d_col[i], d_coeff[i]};
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_SPMV);
+        return launch_r1cs_check<Fr>(ctx->stream, m[0], m[1], m[2], n_rows, nnz_total, (int)form, (const Fr*)d_witness, (unsigned long long*)d_result);
+    });
+}
+int32_t cg_qap_columns_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_col_ptr, const uint32_t* d_row, const void* d_coeff, size_t n_cols, uint32_t long_min,
+                           const void* d_lagrange, void* d_out) {
+    if (!ctx || (n_cols && (!d_col_ptr || !d_lagrange || !d_out))) return fail(CG_ERR_ARG, "null argument");
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_SPMV);
+        return launch_qap_columns<Fr>(ctx->stream, d_col_ptr, d_row, (const Fr*)d_coeff, n_cols, (const Fr*)d_lagrange, (Fr*)d_out, long_min);
+    });
+}
+
 static int32_t host_vec_call(cg_ctx* ctx, size_t n, int n_in, const void* const* h_in, void* h_out, int (*fn)(cg_ctx*, void* const*, void*, size_t, int), int curve) {
     if (!ctx || !h_out) return fail(CG_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(ctx->device));

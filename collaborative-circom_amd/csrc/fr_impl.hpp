@@ -4,6 +4,7 @@
 #include "ntt_kernels.hpp"
 #include "vec_kernels.hpp"
 #include "plonk_kernels.hpp"
+#include "r1cs_kernels.hpp"
 #include "msm_sort_kernels.hpp"
 
 namespace cg {
@@ -121,6 +122,25 @@ template <class Fr> int launch_spmv_csr(hipStream_t st, const uint32_t* row_ptr,
     if (!n_rows) return 0;
     if (n_rows <= ((size_t)1 << 13)) hipLaunchKernelGGL((k_spmv_csr_wave<Fr>), dim3(grid_for(n_rows * 64)), dim3(256), 0, st, row_ptr, col, coeff, n_rows, pub, n_inputs, party, wit_a, wit_b, out_a, out_b);   // a wave per row
     else hipLaunchKernelGGL((k_spmv_csr<Fr>), dim3(grid_for(n_rows)), dim3(256), 0, st, row_ptr, col, coeff, n_rows, pub, n_inputs, party, wit_a, wit_b, out_a, out_b);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// witness check: a wave per row triple when the rows cannot fill the chip with a lane each (as launch_spmv_csr) or when the mean row is long
+// (>= 32 terms per matrix: a lane would walk them one by one while its 63 neighbours wait for the longest row of the wave)
+template <class Fr> int launch_r1cs_check(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, size_t nnz_total, int form, const Fr* w,
+                                          unsigned long long* result) {
+    static const unsigned long long init[2] = {0ull, ~0ull};
+    HIPCHK(hipMemcpyAsync(result, init, sizeof init, hipMemcpyHostToDevice, st));
+    if (!n_rows) return 0;
+    const bool wave = form == 2 || (form == 0 && (n_rows <= ((size_t)1 << 13) || nnz_total / n_rows >= 96));
+    if (wave) hipLaunchKernelGGL((k_r1cs_check_wave<Fr>), dim3(grid_for(n_rows * 64)), dim3(256), 0, st, A, B, C, n_rows, w, result);
+    else hipLaunchKernelGGL((k_r1cs_check<Fr>), dim3(grid_for(n_rows)), dim3(256), 0, st, A, B, C, n_rows, w, result);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+template <class Fr> int launch_qap_columns(hipStream_t st, const uint32_t* col_ptr, const uint32_t* row, const Fr* coeff, size_t n_cols, const Fr* L, Fr* out, uint32_t long_min) {
+    if (!n_cols) return 0;
+    hipLaunchKernelGGL((k_qap_columns<Fr>), dim3(grid_for(n_cols)), dim3(256), 0, st, col_ptr, row, coeff, n_cols, L, out, long_min ? long_min : QAP_LONG_COLUMN);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -306,6 +326,8 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     template decltype(launch_plonk_r3_t<Fr>) launch_plonk_r3_t<Fr>;                                                        \
     template decltype(launch_plonk_r3_divide<Fr>) launch_plonk_r3_divide<Fr>;                                              \
     template decltype(launch_spmv_csr<Fr>) launch_spmv_csr<Fr>;                                                            \
+    template decltype(launch_r1cs_check<Fr>) launch_r1cs_check<Fr>;                                                        \
+    template decltype(launch_qap_columns<Fr>) launch_qap_columns<Fr>;                                                      \
     template decltype(launch_build_twiddles_lazy<Fr>) launch_build_twiddles_lazy<Fr>;                                      \
     template decltype(launch_ntt_ct_pass<Fr>) launch_ntt_ct_pass<Fr>;                                                      \
     template decltype(launch_build_twiddles_lazy_natural<Fr>) launch_build_twiddles_lazy_natural<Fr>;                      \

@@ -72,6 +72,13 @@ template <class Fr> int launch_prefix_scan(hipStream_t st, int op, Fr* out, cons
 template <class Fr> int launch_vec_inverse(hipStream_t st, Fr* out, const Fr* in, size_t n);
 template <class Fr> int launch_spmv_csr(hipStream_t st, const uint32_t* row_ptr, const uint32_t* col, const Fr* coeff, size_t n_rows, const Fr* pub,
                                         uint32_t n_inputs, int party, const Fr* wit_a, const Fr* wit_b, Fr* out_a, Fr* out_b);
+// r1cs_kernels.hpp.  form: 0 = chosen from the row count and the mean row length (nnz_total terms over the three matrices, 0 = unknown),
+// 1 = a lane per row triple, 2 = a wave per row triple.  result: count, smallest failing row (both set by the launcher first).
+struct R1csMat { const uint32_t* row_ptr; const uint32_t* col; const void* coeff; };   // CSR, coefficients in Montgomery form
+constexpr uint32_t QAP_LONG_COLUMN = 64;   // k_qap_columns: entries from which the workgroup, not one lane, sums a column
+template <class Fr> int launch_r1cs_check(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, size_t nnz_total, int form, const Fr* w,
+                                          unsigned long long* result);
+template <class Fr> int launch_qap_columns(hipStream_t st, const uint32_t* col_ptr, const uint32_t* row, const Fr* coeff, size_t n_cols, const Fr* L, Fr* out, uint32_t long_min);
 template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* order, size_t n, const uint32_t* ids, const Fr* coeffs, const Fr* pub, uint32_t n_inputs, int pc,
                                                Fr* ext_a, Fr* ext_b, size_t n_priv);
 template <class Fr> int launch_plonk_r2_factors(hipStream_t st, const PlonkR2Args<Fr>& g, size_t n);

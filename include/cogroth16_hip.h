@@ -320,6 +320,21 @@ int32_t cg_vec_inverse_dev(cg_ctx* ctx, int32_t curve, void* d_out, const void* 
 int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeff,
                         size_t n_rows, const void* d_pub, uint32_t n_inputs, int32_t party,
                         const void* d_wit_a, const void* d_wit_b, void* d_out_a, void* d_out_b);
+/* R1CS witness check in one pass, no intermediate vectors: d_result[0] = the number of rows i < n_rows with <A_i,w> * <B_i,w> != <C_i,w>,
+ * d_result[1] = the smallest such row, 2^64 - 1 when there is none (two u64; the call initialises them).  d_row_ptr / d_col / d_coeff:
+ * three entries each (A, B, C), CSR with n_rows + 1 row pointers, Montgomery coefficients; d_witness: the PLAIN full witness (wire 0 = one),
+ * indexed by the column ids — the caller guarantees col < its length.  Secret-shared witnesses are out of scope: a product of shares is
+ * not a share of the product without a protocol round.  form: 0 = chosen by size (a wave per row triple up to 2^13 rows or from a mean of
+ * 96 terms per row triple, nnz_total = terms of the three matrices together, 0 = unknown), 1 = a lane per row triple, 2 = a wave per row
+ * triple (strided terms, cross-lane field sums); both forms give the same result.  Failures are counted per wave, one atomic per workgroup. */
+int32_t cg_r1cs_check_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff,
+                          size_t n_rows, size_t nnz_total, int32_t form, const void* d_witness, void* d_result);
+/* QAP column sums of one constraint matrix (Groth16 setup): d_out[i] = sum_j M[j][i] * L_j for every column i < n_cols, from the matrix in
+ * column-major form (d_col_ptr: n_cols + 1 offsets, d_row / d_coeff: row id and Montgomery coefficient per entry, row < length of
+ * d_lagrange).  No atomics on field elements: a lane sums a column of fewer than long_min entries (0 = the default, 64), a longer one —
+ * the constant wire of a real circuit sits in a large share of the rows — is split over its workgroup's 256 lanes and reduced. */
+int32_t cg_qap_columns_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_col_ptr, const uint32_t* d_row, const void* d_coeff, size_t n_cols,
+                           uint32_t long_min, const void* d_lagrange, void* d_out);
 /* co-plonk, every share component of a vector in one launch.  k = share components (REP3 2, plain / Shamir 1); pointer tables hold
  * [vector * 2 + component] (entries of component 1 are ignored when k == 1); public_component = the component that holds public
  * addends (plain / Shamir 0, REP3 party 0 -> 0, party 1 -> 1, party 2 -> -1).  Vectors are device-resident Montgomery elements.

@@ -1,7 +1,7 @@
 /* cogroth16_host.h — C ABI of the host mirror (libcogroth16_host.so): the co-circom prover entry points on top of cogroth16_hip.h.
  *
  * The reference is Rust and cannot be built in this image (no cargo), so the host side above the kernel ABI is C++
- * (collaborative-circom_amd/host/ (headers per layer: formats, network, driver, groth16, plonk, codecs, synth; entry points in capi_*.cpp)): drivers PlainHipDriver / Rep3HipProtocol / ShamirHipProtocol with the method names of
+ * (collaborative-circom_amd/host/ (headers per layer: formats, network, driver, groth16, plonk, codecs, synth, r1cs; entry points in capi_*.cpp)): drivers PlainHipDriver / Rep3HipProtocol / ShamirHipProtocol with the method names of
  * the reference's traits (mpc-core/src/traits.rs:43-223, 535-568), CoGroth16::prove (co-groth16/src/groth16.rs:113-326) and CoPlonk
  * rounds 1-5 (co-plonk/src/round{1..5}.rs) with the reference's call sequence, in-process REP3 / Shamir networks in the role of
  * tests/src/rep3_network.rs, and the readers / writers of the file formats (circom-types).  These entry points are what the CLI's
@@ -359,6 +359,35 @@ int32_t cgh_synth_circuit(int32_t device, int32_t curve, int32_t log_m, uint64_t
  * 1-14, p_tau = n + 6 points) + .wtns: n_public >= 1 public-input rows, multiplication / addition / constant gates with fan-out, n_additions
  * additions in chains six deep (some over public inputs), identity permutation on the padding rows */
 int32_t cgh_synth_plonk_circuit(int32_t device, int32_t curve, int32_t log_n, uint64_t seed, uint32_t n_public, uint32_t n_additions, const char* zkey_path, const char* wtns_path);
+
+/* ---- R1CS: reader, witness check on the GPU, development keys (host/r1cs.hpp) -------------------------------------------------
+ * An .r1cs handle holds the three constraint matrices of an iden3 .r1cs file, version 1 (the format circom-types/src/r1cs.rs reads), as CSR
+ * with Montgomery coefficients in the file's term order.  Opening refuses, with a status and a cgh_last_error text: a wrong magic or version,
+ * a field size other than 32, a prime that is not the curve's r, a section that ends outside the file, a missing or duplicate section 1 or 2,
+ * a term count that runs past its section, a wire id >= nWires, a value >= r, nPublic + 1 > nWires.  Section 3 and unknown sections are
+ * skipped by their length.  info[7]: n_wires, n_public (= nPubOut + nPubIn), n_constraints, domain size (the power of two from
+ * n_constraints + n_public + 1 that Groth16 uses), nnz(A), nnz(B), nnz(C).  One call at a time per handle. */
+int32_t cgh_r1cs_open(int32_t curve, const char* path, void** out_r1cs);
+int32_t cgh_r1cs_info(void* r1cs, size_t* info);
+int32_t cgh_r1cs_close(void* r1cs);
+/* Section 4 of the Groth16 zkey the circuit determines (u32 count, then (u32 matrix, u32 row, u32 wire, coefficient * R^2) records: per
+ * constraint its A terms then its B terms in the file's order, then A[nC + s][s] = 1 for s = 0 .. n_public) — byte-equal to what snarkjs
+ * writes.  Host only.  *n_bytes = its size; out == NULL: only the size. */
+int32_t cgh_r1cs_coeff_section(void* r1cs, uint8_t* out, size_t cap, size_t* n_bytes);
+/* Does the PLAIN full witness (n_wires Montgomery elements, wire 0 = one) satisfy the circuit?  One kernel pass on the GPU `device`
+ * (cg_r1cs_check_dev): *n_bad = the number of constraints i with <A_i,w> * <B_i,w> != <C_i,w>, *first_bad = the smallest such i, 2^64 - 1
+ * when there is none.  The matrices are uploaded at the first call per device and stay there until the handle closes.  A circom zkey drops
+ * C, so only the R1CS can answer this without a proof.  Secret-shared witnesses are OUT OF SCOPE: the check multiplies two sums of witness
+ * values, which no party can do on shares alone.  _form: the kernel form of cg_r1cs_check_dev (0 = chosen by size, what the plain entry uses). */
+int32_t cgh_r1cs_check_witness(int32_t device, void* r1cs, const uint64_t* full_witness, uint64_t* n_bad, uint64_t* first_bad);
+int32_t cgh_r1cs_check_witness_form(int32_t device, void* r1cs, int32_t form, const uint64_t* full_witness, uint64_t* n_bad, uint64_t* first_bad);
+/* A snarkjs-format Groth16 .zkey (sections 1-9, the layout cgh_synth_circuit writes) for the circuit, from toxic waste tau, alpha, beta,
+ * gamma, delta derived from `seed`; the field vectors, the column sums of A, B, C (cg_qap_columns_dev) and the five point tables are
+ * computed on the GPU.  FOR DEVELOPMENT ONLY — tests, benches, demos: whoever knows the seed knows the toxic waste and can forge proofs
+ * that verify under this key.  Never use such a key where soundness matters; production keys come from a ceremony.
+ * cgh_setup_toxic: the five values for a seed (Montgomery: tau, alpha, beta, gamma, delta), so that a test can recompute key elements. */
+int32_t cgh_setup_groth16_dev(int32_t device, void* r1cs, uint64_t seed, const char* zkey_path);
+int32_t cgh_setup_toxic(int32_t curve, uint64_t seed, uint64_t* out5);
 
 /* ---- Plonk verification (co-plonk/src/plonk.rs:133-271; host/plonk_verify.hpp) ---------------------------------------------
  * A verifying-key handle holds nPublic, power, k1, k2, Qm, Ql, Qr, Qo, Qc, S1, S2, S3 and X_2 from a verification_key.json (the fields
