@@ -55,7 +55,7 @@ ABI_SYMBOLS = [
     "cg_ntt", "cg_ntt_dev", "cg_ntt_coset_pair_dev", "cg_chacha12_fr_rand_dev", "cg_chacha12_fr_rand_dev_begin", "cg_chacha12_fr_rand_dev_finish",
     "cg_host_alloc", "cg_host_free", "cg_host_is_pinned", "cg_dev_download_begin", "cg_dev_upload_begin", "cg_stream_mark", "cg_dev_download_begin_after", "cg_copy_wait", "cg_copy_fence",
     "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_shamir_share_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
-    "cg_spmv_csr_dev", "cg_r1cs_check_dev", "cg_qap_columns_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
+    "cg_spmv_csr_dev", "cg_r1cs_check_dev", "cg_qap_columns_dev", "cg_plonk_gates_count_dev", "cg_plonk_gates_emit_dev", "cg_plonk_sigma_labels_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
     "cg_plonk_additions_dev", "cg_plonk_r2_factors_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
@@ -556,6 +556,26 @@ class Context:
         which the workgroup, not one lane, sums a column (0 = the library's default)"""
         _chk(load().cg_qap_columns_dev(self.h, curve, _dp(col_ptr), _dp(row), _dp(coeff), C.c_size_t(n_cols), C.c_uint32(long_min), _dp(lagrange), _dp(out)))
 
+    def plonk_gates_count(self, curve, mats, n_rows, nnz_total, counts, offsets):
+        """cg_plonk_gates_count_dev: mats = three canonical (row_ptr, col, coeff) device triples (wires ascending, merged, no zero coefficient);
+        counts / offsets = device buffers of n_rows + 1 u32 (additions per row, their exclusive scan); returns the additions of the circuit"""
+        total = C.c_size_t(0)
+        _chk(load().cg_plonk_gates_count_dev(self.h, curve, _ptr_list([m[0] for m in mats]), _ptr_list([m[1] for m in mats]), _ptr_list([m[2] for m in mats]),
+                                             C.c_size_t(n_rows), C.c_size_t(nnz_total), _dp(counts), _dp(offsets), C.byref(total)))
+        return int(total.value)
+
+    def plonk_gates_emit(self, curve, mats, n_rows, n_wires, n_public, counts, offsets, n_additions, domain_size, maps, q, add_ids, add_f):
+        """cg_plonk_gates_emit_dev: maps = 3 device buffers of n_public + n_rows + n_additions u32, q = 5 device vectors of domain_size elements
+        (qm, ql, qr, qo, qc), add_ids / add_f = 2 u32 / 2 elements per addition"""
+        _chk(load().cg_plonk_gates_emit_dev(self.h, curve, _ptr_list([m[0] for m in mats]), _ptr_list([m[1] for m in mats]), _ptr_list([m[2] for m in mats]),
+                                            C.c_size_t(n_rows), C.c_size_t(n_wires), C.c_size_t(n_public), _dp(counts), _dp(offsets), C.c_size_t(n_additions),
+                                            C.c_size_t(domain_size), _ptr_list(maps), _ptr_list(q), _dp(add_ids), _dp(add_f)))
+
+    def plonk_sigma_labels(self, curve, prev, omega_powers, domain_size, k1, k2, sigma):
+        """cg_plonk_sigma_labels_dev: sigma[p] = k_(prev[p] / n) * omega_powers[prev[p] % n] for p < 3n"""
+        _chk(load().cg_plonk_sigma_labels_dev(self.h, curve, _dp(prev), _dp(omega_powers), C.c_size_t(domain_size), _hp(np.ascontiguousarray(k1, dtype=np.uint64)),
+                                              _hp(np.ascontiguousarray(k2, dtype=np.uint64)), _dp(sigma)))
+
     def spmv_csr(self, curve, row_ptr, col, coeff, n_rows, pub, n_inputs, party, wit_a, wit_b, out_a, out_b):
         _chk(load().cg_spmv_csr_dev(self.h, curve, _dp(row_ptr), _dp(col), _dp(coeff), C.c_size_t(n_rows), _dp(pub), C.c_uint32(n_inputs), int(party),
                                     _dp(wit_a), _dp(wit_b), _dp(out_a), _dp(out_b)))
@@ -922,11 +942,38 @@ class R1cs:
         _hchk(load_host().cgh_r1cs_check_witness_form(int(device), self.h, int(form), _hp(w), C.byref(n_bad), C.byref(first)))
         return int(n_bad.value), int(first.value)
 
+    def plonk_info(self, device=0):
+        """sizes of the Plonk key of this circuit (cgh_r1cs_plonk_info, the count pass of the gate compiler on the GPU): dict of n_additions,
+        n_constraints, n_vars, domain_size"""
+        out = (C.c_size_t * 4)()
+        _hchk(load_host().cgh_r1cs_plonk_info(int(device), self.h, out))
+        return dict(zip(("n_additions", "n_constraints", "n_vars", "domain_size"), [int(x) for x in out]))
+
 
 def setup_groth16(r1cs, seed, zkey_path, device=0):
     """a snarkjs-format Groth16 .zkey for the circuit from seeded toxic waste (cgh_setup_groth16_dev), computed on the GPU.
     DEVELOPMENT ONLY: whoever holds the seed can forge proofs for this key."""
     _hchk(load_host().cgh_setup_groth16_dev(int(device), r1cs.h, C.c_uint64(seed), zkey_path.encode()))
+
+
+PLONK_SETUP_STAGES = ("count", "emit", "sigma", "transforms", "points", "lagrange", "write")
+
+
+def setup_plonk(r1cs, seed, zkey_path, device=0, timing=False):
+    """a snarkjs-format Plonk .zkey for the circuit (cgh_setup_plonk_dev): gates, permutation and polynomials as snarkjs' `plonk setup` makes
+    them, computed on the GPU; the points from tau = setup_toxic(curve, seed)[0].  timing=True returns the seconds per stage
+    (PLONK_SETUP_STAGES, through cgh_setup_plonk_tau_dev).
+    DEVELOPMENT ONLY: the seed is the toxic waste, whoever holds it can forge proofs for this key."""
+    if timing:
+        return setup_plonk_tau(r1cs, setup_toxic(r1cs.curve, seed)[0], zkey_path, device=device, timing=True)
+    _hchk(load_host().cgh_setup_plonk_dev(int(device), r1cs.h, C.c_uint64(seed), None if zkey_path is None else zkey_path.encode()))
+
+
+def setup_plonk_tau(r1cs, tau, zkey_path, device=0, timing=False):
+    """setup_plonk with tau given (4 Montgomery limbs) instead of drawn from a seed (cgh_setup_plonk_tau_dev).  DEVELOPMENT ONLY."""
+    secs = (C.c_double * len(PLONK_SETUP_STAGES))() if timing else None
+    _hchk(load_host().cgh_setup_plonk_tau_dev(int(device), r1cs.h, _hp(np.ascontiguousarray(tau, dtype=np.uint64).reshape(4)), zkey_path.encode(), secs))
+    return dict(zip(PLONK_SETUP_STAGES, secs)) if timing else None
 
 
 def setup_toxic(curve, seed):

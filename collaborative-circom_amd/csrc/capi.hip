@@ -727,6 +727,72 @@ int32_t cg_qap_columns_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_col_ptr
     });
 }
 
+// Plonk setup (plonk_setup_kernels.hpp)
+static int plonk_gate_mats(const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff, R1csMat* m) {
+    if (!d_row_ptr || !d_col || !d_coeff) return fail(CG_ERR_ARG, "null argument");
+    for (int i = 0; i < 3; i++) {
+        if (!d_row_ptr[i]) return fail(CG_ERR_ARG, "null row pointers");
+        m[i] = R1csMat{d_row_ptr[i], d_col[i], d_coeff[i]};
+    }
+    return 0;
+}
+int32_t cg_plonk_gates_count_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff, size_t n_rows,
+                                 size_t nnz_total, uint32_t* d_counts, uint32_t* d_offsets, size_t* n_additions) {
+    if (!ctx || !d_counts || !d_offsets || !n_additions) return fail(CG_ERR_ARG, "null argument");
+    if ((n_rows >> 32) || (nnz_total >> 32)) return fail(CG_ERR_ARG, "cg_plonk_gates_count_dev: rows and terms must stay below 2^32 (the additions are counted in 32 bits)");
+    R1csMat m[3];
+    if (int rc = plonk_gate_mats(d_row_ptr, d_col, d_coeff, m)) return rc;
+    HIPCHK(hipSetDevice(ctx->device));
+    void* tiles = nullptr;
+    HIPCHK(hip_malloc_flush(&tiles, ((n_rows + 1 + SCAN_TILE - 1) / SCAN_TILE) * 4));
+    int rc = with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_SPMV);
+        return launch_plonk_gate_count<Fr>(ctx->stream, m[0], m[1], m[2], n_rows, d_counts, d_offsets, (uint32_t*)tiles);
+    });
+    uint32_t total = 0;
+    if (!rc && hipMemcpyAsync(&total, d_offsets + n_rows, 4, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = fail(CG_ERR_HIP, "cg_plonk_gates_count_dev: download of the total");
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(tiles);
+    if (rc) return rc;
+    HIPCHK(e);
+    *n_additions = total;
+    return 0;
+}
+int32_t cg_plonk_gates_emit_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff, size_t n_rows,
+                                size_t n_wires, size_t n_public, const uint32_t* d_counts, const uint32_t* d_offsets, size_t n_additions, size_t domain_size,
+                                uint32_t* const* d_maps, void* const* d_q, uint32_t* d_add_ids, void* d_add_f) {
+    if (!ctx || !d_counts || !d_offsets || !d_maps || !d_q || !d_add_ids || !d_add_f) return fail(CG_ERR_ARG, "null argument");
+    R1csMat m[3];
+    if (int rc = plonk_gate_mats(d_row_ptr, d_col, d_coeff, m)) return rc;
+    const size_t n_constraints = n_public + n_rows + n_additions;
+    if (((n_wires + n_additions) >> 32) || n_public >= n_wires) return fail(CG_ERR_ARG, "cg_plonk_gates_emit_dev: the signals (wires + additions) must fit 32 bits, the public ones the wires");
+    if (domain_size < n_constraints) return fail(CG_ERR_ARG, "cg_plonk_gates_emit_dev: the domain is smaller than public inputs + rows + additions");
+    PlonkGateOut o;
+    for (int i = 0; i < 3; i++) { if (!d_maps[i]) return fail(CG_ERR_ARG, "null map"); o.map[i] = d_maps[i]; }
+    for (int i = 0; i < 5; i++) { if (!d_q[i]) return fail(CG_ERR_ARG, "null selector vector"); o.q[i] = d_q[i]; }
+    o.add_ids = d_add_ids; o.add_f = d_add_f;
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_SPMV);
+        return launch_plonk_gate_emit<Fr>(ctx->stream, m[0], m[1], m[2], n_rows, (uint32_t)n_wires, (uint32_t)n_public, d_counts, d_offsets, n_constraints, domain_size, o);
+    });
+}
+int32_t cg_plonk_sigma_labels_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_prev, const void* d_omega_powers, size_t domain_size, const void* h_k1, const void* h_k2, void* d_sigma) {
+    if (!ctx || !d_prev || !d_omega_powers || !h_k1 || !h_k2 || !d_sigma) return fail(CG_ERR_ARG, "null argument");
+    int log_n = 0;
+    while (((size_t)1 << log_n) < domain_size) log_n++;
+    if (((size_t)1 << log_n) != domain_size || log_n > 30) return fail(CG_ERR_ARG, "cg_plonk_sigma_labels_dev: the domain must be a power of two of at most 2^30");
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_SPMV);
+        Fr k1, k2; copy_in(k1, h_k1); copy_in(k2, h_k2);
+        return launch_plonk_sigma_labels<Fr>(ctx->stream, d_prev, (const Fr*)d_omega_powers, log_n, k1, k2, (Fr*)d_sigma);
+    });
+}
+
 static int32_t host_vec_call(cg_ctx* ctx, size_t n, int n_in, const void* const* h_in, void* h_out, int (*fn)(cg_ctx*, void* const*, void*, size_t, int), int curve) {
     if (!ctx || !h_out) return fail(CG_ERR_ARG, "null argument");
     HIPCHK(hipSetDevice(ctx->device));

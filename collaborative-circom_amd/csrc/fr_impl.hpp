@@ -5,6 +5,7 @@
 #include "vec_kernels.hpp"
 #include "plonk_kernels.hpp"
 #include "r1cs_kernels.hpp"
+#include "plonk_setup_kernels.hpp"
 #include "msm_sort_kernels.hpp"
 
 namespace cg {
@@ -141,6 +142,29 @@ template <class Fr> int launch_r1cs_check(hipStream_t st, const R1csMat& A, cons
 template <class Fr> int launch_qap_columns(hipStream_t st, const uint32_t* col_ptr, const uint32_t* row, const Fr* coeff, size_t n_cols, const Fr* L, Fr* out, uint32_t long_min) {
     if (!n_cols) return 0;
     hipLaunchKernelGGL((k_qap_columns<Fr>), dim3(grid_for(n_cols)), dim3(256), 0, st, col_ptr, row, coeff, n_cols, L, out, long_min ? long_min : QAP_LONG_COLUMN);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// Plonk setup: the addition count of every row and its exclusive scan (k_scan_*: tiles of SCAN_TILE counters), then the gates
+template <class Fr> int launch_plonk_gate_count(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, uint32_t* counts, uint32_t* offsets, uint32_t* tile_sums) {
+    const size_t total = n_rows + 1, ntiles = (total + SCAN_TILE - 1) / SCAN_TILE;
+    HIPCHK(hipMemsetAsync(counts + n_rows, 0, 4, st));
+    if (n_rows) hipLaunchKernelGGL((k_plonk_gate_count<Fr>), dim3(grid_for(n_rows)), dim3(256), 0, st, A, B, C, n_rows, counts);
+    hipLaunchKernelGGL(k_scan_tile_sums, dim3((unsigned)ntiles), dim3(256), 0, st, counts, tile_sums, total, 0xffffffffu);
+    hipLaunchKernelGGL(k_scan_exclusive, dim3(1), dim3(1024), 0, st, tile_sums, tile_sums, ntiles);
+    hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, st, counts, tile_sums, offsets, total, 0xffffffffu);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+template <class Fr> int launch_plonk_gate_emit(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, uint32_t n_wires, uint32_t n_public,
+                                               const uint32_t* counts, const uint32_t* offsets, size_t n_constraints, size_t n, const PlonkGateOut& o) {
+    for (int i = 0; i < 5; i++) if (n > n_constraints) HIPCHK(hipMemsetAsync((Fr*)o.q[i] + n_constraints, 0, (n - n_constraints) * sizeof(Fr), st));
+    if (n_rows + n_public) hipLaunchKernelGGL((k_plonk_gate_emit<Fr>), dim3(grid_for(n_rows + n_public)), dim3(256), 0, st, A, B, C, n_rows, n_wires, n_public, counts, offsets, o);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+template <class Fr> int launch_plonk_sigma_labels(hipStream_t st, const uint32_t* prev, const Fr* wpow, int log_n, const Fr& k1, const Fr& k2, Fr* sigma) {
+    hipLaunchKernelGGL((k_plonk_sigma_labels<Fr>), dim3(grid_for((size_t)3 << log_n)), dim3(256), 0, st, prev, wpow, log_n, k1, k2, sigma);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -328,6 +352,9 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     template decltype(launch_spmv_csr<Fr>) launch_spmv_csr<Fr>;                                                            \
     template decltype(launch_r1cs_check<Fr>) launch_r1cs_check<Fr>;                                                        \
     template decltype(launch_qap_columns<Fr>) launch_qap_columns<Fr>;                                                      \
+    template decltype(launch_plonk_gate_count<Fr>) launch_plonk_gate_count<Fr>;                                            \
+    template decltype(launch_plonk_gate_emit<Fr>) launch_plonk_gate_emit<Fr>;                                              \
+    template decltype(launch_plonk_sigma_labels<Fr>) launch_plonk_sigma_labels<Fr>;                                        \
     template decltype(launch_build_twiddles_lazy<Fr>) launch_build_twiddles_lazy<Fr>;                                      \
     template decltype(launch_ntt_ct_pass<Fr>) launch_ntt_ct_pass<Fr>;                                                      \
     template decltype(launch_build_twiddles_lazy_natural<Fr>) launch_build_twiddles_lazy_natural<Fr>;                      \

@@ -79,6 +79,20 @@ constexpr uint32_t QAP_LONG_COLUMN = 64;   // k_qap_columns: entries from which 
 template <class Fr> int launch_r1cs_check(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, size_t nnz_total, int form, const Fr* w,
                                           unsigned long long* result);
 template <class Fr> int launch_qap_columns(hipStream_t st, const uint32_t* col_ptr, const uint32_t* row, const Fr* coeff, size_t n_cols, const Fr* L, Fr* out, uint32_t long_min);
+// plonk_setup_kernels.hpp: the gate compiler of the Plonk setup over the canonical CSR (wires ascending, merged, no zero coefficient).
+// count: counts[n_rows + 1] (the last entry 0) and their exclusive scan offsets[n_rows + 1] (the last entry = the additions of the circuit);
+// tile_sums: ceil((n_rows + 1) / SCAN_TILE) counters of scratch.  emit: the gates, public-input rows first; q rows from n_constraints to
+// n are zeroed.  sigma: 3n labels from the previous positions.
+struct PlonkGateOut {
+    uint32_t* map[3];        // n_constraints each
+    void* q[5];              // qm, ql, qr, qo, qc: n rows each, Montgomery
+    uint32_t* add_ids;       // 2 per addition
+    void* add_f;             // 2 per addition, Montgomery
+};
+template <class Fr> int launch_plonk_gate_count(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, uint32_t* counts, uint32_t* offsets, uint32_t* tile_sums);
+template <class Fr> int launch_plonk_gate_emit(hipStream_t st, const R1csMat& A, const R1csMat& B, const R1csMat& C, size_t n_rows, uint32_t n_wires, uint32_t n_public,
+                                               const uint32_t* counts, const uint32_t* offsets, size_t n_constraints, size_t n, const PlonkGateOut& o);
+template <class Fr> int launch_plonk_sigma_labels(hipStream_t st, const uint32_t* prev, const Fr* wpow, int log_n, const Fr& k1, const Fr& k2, Fr* sigma);
 template <class Fr> int launch_plonk_additions(hipStream_t st, const uint32_t* order, size_t n, const uint32_t* ids, const Fr* coeffs, const Fr* pub, uint32_t n_inputs, int pc,
                                                Fr* ext_a, Fr* ext_b, size_t n_priv);
 template <class Fr> int launch_plonk_r2_factors(hipStream_t st, const PlonkR2Args<Fr>& g, size_t n);

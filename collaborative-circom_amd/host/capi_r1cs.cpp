@@ -1,5 +1,5 @@
-// C entry points: .r1cs handles, the witness check, the Groth16 development setup (include/cogroth16_host.h)
-#include "r1cs.hpp"
+// C entry points: .r1cs handles, the witness check, the Groth16 and Plonk development setups (include/cogroth16_host.h)
+#include "plonk_setup.hpp"
 #include "capi_common.hpp"
 
 extern "C" {
@@ -58,6 +58,31 @@ int32_t cgh_setup_toxic(int32_t curve, uint64_t seed, uint64_t* out5) {
         if (curve != CG_BN254 && curve != CG_BLS12_381) throw std::runtime_error("cgh_setup_toxic: unknown curve");
         cgh::Fr t[5]; cgh::setup_toxic(cgh::Curve{curve}, seed, t);
         memcpy(out5, t, sizeof t);
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
+int32_t cgh_r1cs_plonk_info(int32_t device, void* r1cs, size_t* out4) {
+    try {
+        if (!r1cs || !out4) throw std::runtime_error("cgh_r1cs_plonk_info: null argument");
+        const cgh::PlonkPlan p = cgh::r1cs_plonk_info(*(cgh::R1csHandle*)r1cs, device);
+        out4[0] = p.n_additions; out4[1] = p.n_constraints; out4[2] = p.n_vars; out4[3] = p.n;
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
+int32_t cgh_setup_plonk_dev(int32_t device, void* r1cs, uint64_t seed, const char* zkey_path) {
+    try {
+        if (!r1cs || !zkey_path) throw std::runtime_error("cgh_setup_plonk_dev: null argument");
+        cgh::setup_plonk_dev(*(cgh::R1csHandle*)r1cs, device, seed, zkey_path);
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
+int32_t cgh_setup_plonk_tau_dev(int32_t device, void* r1cs, const uint64_t* tau, const char* zkey_path, double* stage_seconds) {
+    try {
+        if (!r1cs || !tau || !zkey_path) throw std::runtime_error("cgh_setup_plonk_tau_dev: null argument");
+        cgh::Fr t; memcpy(t.v, tau, 32);
+        int32_t canonical = 0;
+        if (cg_fr_is_canonical(((cgh::R1csHandle*)r1cs)->r.curve.id, t.v, 1, &canonical) || !canonical) throw std::runtime_error("cgh_setup_plonk_tau_dev: tau is not below the modulus");
+        cgh::setup_plonk_tau_dev(*(cgh::R1csHandle*)r1cs, device, t, zkey_path, stage_seconds);
         return 0;
     } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
 }

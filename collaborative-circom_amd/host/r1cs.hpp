@@ -112,15 +112,20 @@ struct R1csDevice {
     cg_ctx* ctx = nullptr;
     void* row_ptr[3] = {nullptr, nullptr, nullptr}; void* col[3] = {nullptr, nullptr, nullptr}; void* coeff[3] = {nullptr, nullptr, nullptr};
     void* witness = nullptr; void* result = nullptr;
+    void* canon_row_ptr[3] = {nullptr, nullptr, nullptr}; void* canon_col[3] = {nullptr, nullptr, nullptr}; void* canon_coeff[3] = {nullptr, nullptr, nullptr};   // plonk_setup.hpp
 };
+// the matrices in the canonical form of the Plonk gate compiler (plonk_setup.hpp): inside a row the wires ascend, a wire named twice is one
+// term, no coefficient is zero.  Built at the first Plonk call on the handle.
+struct R1csCanonical { bool built = false; std::vector<uint32_t> row_ptr[3], col[3]; std::vector<Fr> coeff[3]; };
 struct R1csHandle {
     R1cs r;
+    R1csCanonical canon;
     std::mutex mu;
     std::map<int, R1csDevice> dev;
     ~R1csHandle() {
         for (auto& kv : dev) {
             R1csDevice& d = kv.second;
-            for (int m = 0; m < 3; m++) for (void* p : {d.row_ptr[m], d.col[m], d.coeff[m]}) if (p) cg_dev_free(d.ctx, p);
+            for (int m = 0; m < 3; m++) for (void* p : {d.row_ptr[m], d.col[m], d.coeff[m], d.canon_row_ptr[m], d.canon_col[m], d.canon_coeff[m]}) if (p) cg_dev_free(d.ctx, p);
             if (d.witness) cg_dev_free(d.ctx, d.witness);
             if (d.result) cg_dev_free(d.ctx, d.result);
             if (d.ctx) cg_ctx_destroy(d.ctx);

@@ -335,6 +335,27 @@ int32_t cg_r1cs_check_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_r
  * the constant wire of a real circuit sits in a large share of the rows — is split over its workgroup's 256 lanes and reduced. */
 int32_t cg_qap_columns_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_col_ptr, const uint32_t* d_row, const void* d_coeff, size_t n_cols,
                            uint32_t long_min, const void* d_lagrange, void* d_out);
+/* Plonk setup: snarkjs' R1CS -> Plonk gate compiler, a lane per constraint.  The three matrices (A, B, C as for cg_r1cs_check_dev) must be
+ * in CANONICAL form: inside a row the wires ascend strictly (a wire named twice merged into one term) and no coefficient is zero, so the
+ * constant - wire 0 - comes first.  A row whose A or B is empty becomes a sum gate on C; one whose A (else B) is a constant k a sum gate on
+ * k * B - C (k * A - C), terms that cancel dropped; every other row a multiplication gate.  A combination longer than the gate takes (3 terms
+ * of a sum, 1 per side of a product) is shortened by "additions": new wires base, base + 1, .. each the sum of the two oldest entries of
+ * the combination's queue, each with a gate (qo = 1, ql = -c_l, qr = -c_r) in front of the row's own gate.
+ *   _count: d_counts[i] = the additions of row i, d_offsets[i] = those of the rows before it (both n_rows + 1 entries: the last count is 0,
+ *           the last offset the total, also returned in *n_additions after a synchronisation).  nnz_total = terms of the three matrices.
+ *   _emit:  with n_constraints = n_public + n_rows + n_additions <= domain_size: gate j < n_public is the public-input gate of signal
+ *           j + 1 (ql = 1); row i writes from gate n_public + i + d_offsets[i], addition record d_offsets[i] and signal n_wires + d_offsets[i]
+ *           on.  d_maps: 3 x n_constraints signal ids (a, b, c); d_q: 5 x domain_size Montgomery elements (qm, ql, qr, qo, qc), rows from
+ *           n_constraints on zeroed; d_add_ids / d_add_f: per addition the two signals read and their two Montgomery coefficients. */
+int32_t cg_plonk_gates_count_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff,
+                                 size_t n_rows, size_t nnz_total, uint32_t* d_counts, uint32_t* d_offsets, size_t* n_additions);
+int32_t cg_plonk_gates_emit_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_row_ptr, const uint32_t* const* d_col, const void* const* d_coeff,
+                                size_t n_rows, size_t n_wires, size_t n_public, const uint32_t* d_counts, const uint32_t* d_offsets, size_t n_additions,
+                                size_t domain_size, uint32_t* const* d_maps, void* const* d_q, uint32_t* d_add_ids, void* d_add_f);
+/* The copy permutation's rows: d_sigma[p] = k_(q / n) * d_omega_powers[q mod n] for q = d_prev[p] < 3n, p < 3n, n = domain_size (a power of
+ * two), (k_0, k_1, k_2) = (1, k1, k2): position p carries the label of the position its signal was seen at before (d_prev, from the host). */
+int32_t cg_plonk_sigma_labels_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_prev, const void* d_omega_powers, size_t domain_size,
+                                  const void* h_k1, const void* h_k2, void* d_sigma);
 /* co-plonk, every share component of a vector in one launch.  k = share components (REP3 2, plain / Shamir 1); pointer tables hold
  * [vector * 2 + component] (entries of component 1 are ignored when k == 1); public_component = the component that holds public
  * addends (plain / Shamir 0, REP3 party 0 -> 0, party 1 -> 1, party 2 -> -1).  Vectors are device-resident Montgomery elements.

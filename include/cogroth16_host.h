@@ -1,7 +1,7 @@
 /* cogroth16_host.h — C ABI of the host mirror (libcogroth16_host.so): the co-circom prover entry points on top of cogroth16_hip.h.
  *
  * The reference is Rust and cannot be built in this image (no cargo), so the host side above the kernel ABI is C++
- * (collaborative-circom_amd/host/ (headers per layer: formats, network, driver, groth16, plonk, codecs, synth, r1cs; entry points in capi_*.cpp)): drivers PlainHipDriver / Rep3HipProtocol / ShamirHipProtocol with the method names of
+ * (collaborative-circom_amd/host/ (headers per layer: formats, network, driver, groth16, plonk, codecs, synth, r1cs, plonk_setup; entry points in capi_*.cpp)): drivers PlainHipDriver / Rep3HipProtocol / ShamirHipProtocol with the method names of
  * the reference's traits (mpc-core/src/traits.rs:43-223, 535-568), CoGroth16::prove (co-groth16/src/groth16.rs:113-326) and CoPlonk
  * rounds 1-5 (co-plonk/src/round{1..5}.rs) with the reference's call sequence, in-process REP3 / Shamir networks in the role of
  * tests/src/rep3_network.rs, and the readers / writers of the file formats (circom-types).  These entry points are what the CLI's
@@ -388,6 +388,24 @@ int32_t cgh_r1cs_check_witness_form(int32_t device, void* r1cs, int32_t form, co
  * cgh_setup_toxic: the five values for a seed (Montgomery: tau, alpha, beta, gamma, delta), so that a test can recompute key elements. */
 int32_t cgh_setup_groth16_dev(int32_t device, void* r1cs, uint64_t seed, const char* zkey_path);
 int32_t cgh_setup_toxic(int32_t curve, uint64_t seed, uint64_t* out5);
+/* Plonk keys from an .r1cs (host/plonk_setup.hpp): snarkjs' `plonk setup` on the GPU.  Each constraint becomes one multiplication
+ * or sum gate behind the "addition" gates that shorten its combinations (cg_plonk_gates_*_dev); combinations are taken by ascending wire
+ * whatever the file's order, a wire named twice in one combination has its coefficients summed.
+ * cgh_r1cs_plonk_info: the count pass only.  out4 = nAdditions, nConstraints (= n_public + constraints + additions), nVars (= n_wires +
+ * additions), the domain size n (the smallest power of two >= nConstraints, at least 8).  Refuses a circuit whose domain exceeds 2^24,
+ * whose 4n evaluation domain exceeds the field's two-adic subgroup, or whose nVars does not fit 32 bits.
+ * cgh_setup_plonk_dev: a snarkjs-format Plonk .zkey (sections 1-14, the layout cgh_synth_plonk_circuit writes) whose header numbers and
+ * sections 3-13 are what snarkjs writes for the circuit; section 14 = [tau^i]_1 for i < n + 6, X_2 = [tau]_2 and the eight commitments
+ * come from tau = the first value of cgh_setup_toxic for `seed`.  FOR DEVELOPMENT ONLY - tests, benches, demos: the seed is the toxic
+ * waste, whoever knows it can forge proofs that verify under this key.  Production keys come from a ceremony (a .ptau), which is out of scope.
+ * Refuses a seed whose tau lies on the domain (tau^n = 1).  _tau_: the same with tau given (Montgomery, nonzero, below the modulus) - what
+ * makes that refusal testable - and, when stage_seconds is not NULL, where the time went, stage_seconds[7]: canonical form + upload + count
+ * pass; emit + download of maps and additions; sigma; transforms of the 8 polynomials + download; p_tau, X_2 and the eight MSMs;
+ * transforms of the Lagrange polynomials; file writes (scripts/plonk_setup_timing.py).
+ * The canonical matrices are uploaded at the first call per device and stay there until the handle closes. */
+int32_t cgh_r1cs_plonk_info(int32_t device, void* r1cs, size_t* out4);
+int32_t cgh_setup_plonk_dev(int32_t device, void* r1cs, uint64_t seed, const char* zkey_path);
+int32_t cgh_setup_plonk_tau_dev(int32_t device, void* r1cs, const uint64_t* tau, const char* zkey_path, double* stage_seconds);
 
 /* ---- Plonk verification (co-plonk/src/plonk.rs:133-271; host/plonk_verify.hpp) ---------------------------------------------
  * A verifying-key handle holds nPublic, power, k1, k2, Qm, Ql, Qr, Qo, Qc, S1, S2, S3 and X_2 from a verification_key.json (the fields
