@@ -53,37 +53,37 @@ int32_t cg_pairing(int32_t curve, const void* h_g1_affine, const void* h_g2_affi
         Affine<typename C::Fq> P; Affine<typename C::Fq2> Q; load_pair<C>(h_g1_affine, h_g2_affine, 0, P, Q);
         Fp12<C> f, e;
         miller_loop(&f, &P, &Q); final_exponentiation(&e, &f);
-        e.store(h_out_fp12); return 0;
+        e.store_host(h_out_fp12); return 0;
     });
 }
 int32_t cg_final_exp(int32_t curve, const void* h_in, void* h_out) {
     if (!h_in || !h_out) return fail(CG_ERR_ARG, "null argument");
     return with_pairing(curve, [&](auto tag) -> int {
         typedef decltype(tag) C;
-        Fp12<C> f = Fp12<C>::load(h_in), e;
+        Fp12<C> f = Fp12<C>::load_host(h_in), e;
         final_exponentiation(&e, &f);
-        e.store(h_out); return 0;
+        e.store_host(h_out); return 0;
     });
 }
 int32_t cg_fp12_mul(int32_t curve, const void* h_a, const void* h_b, void* h_out) {
     if (!h_a || !h_b || !h_out) return fail(CG_ERR_ARG, "null argument");
     return with_pairing(curve, [&](auto tag) -> int {
         typedef decltype(tag) C;
-        const Fp12<C> a = Fp12<C>::load(h_a), b = Fp12<C>::load(h_b);
-        (a * b).store(h_out); return 0;
+        const Fp12<C> a = Fp12<C>::load_host(h_a), b = Fp12<C>::load_host(h_b);
+        (a * b).store_host(h_out); return 0;
     });
 }
 int32_t cg_fp12_pow(int32_t curve, const void* h_a, const void* h_exp, int32_t exp_limbs64, void* h_out) {
     if (!h_a || !h_exp || !h_out || exp_limbs64 < 0) return fail(CG_ERR_ARG, "null argument");
     return with_pairing(curve, [&](auto tag) -> int {
         typedef decltype(tag) C;
-        const Fp12<C> a = Fp12<C>::load(h_a); Fp12<C> r = Fp12<C>::one(), t;
+        const Fp12<C> a = Fp12<C>::load_host(h_a); Fp12<C> r = Fp12<C>::one(), t;
         const uint64_t* e = (const uint64_t*)h_exp;
         for (int b = exp_limbs64 * 64 - 1; b >= 0; b--) {
             fp12_sqr(&t, &r); r = t;
             if ((e[b >> 6] >> (b & 63)) & 1u) { fp12_mul(&t, &r, &a); r = t; }
         }
-        r.store(h_out); return 0;
+        r.store_host(h_out); return 0;
     });
 }
 int32_t cg_miller_loop(int32_t curve, const void* h_g1, const void* h_g2, size_t n, void* h_out_fp12) {
@@ -95,7 +95,7 @@ int32_t cg_miller_loop(int32_t curve, const void* h_g1, const void* h_g2, size_t
             Affine<typename C::Fq> P; Affine<typename C::Fq2> Q; load_pair<C>(h_g1, h_g2, i, P, Q);
             miller_loop(&f, &P, &Q); fp12_mul(&t, &acc, &f); acc = t;
         }
-        acc.store(h_out_fp12); return 0;
+        acc.store_host(h_out_fp12); return 0;
     });
 }
 int32_t cg_pairing_check(int32_t curve, const void* h_g1, const void* h_g2, size_t n, int32_t* ok) {
@@ -139,9 +139,9 @@ int32_t cg_miller_product(cg_ctx* ctx, int32_t curve, const void* h_g1, const vo
             std::vector<uint8_t> part((size_t)groups * sizeof(Fp12<C>));
             HIPCHK(hipMemcpyAsync(part.data(), d_part.p, part.size(), hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipStreamSynchronize(ctx->stream));
-            for (int g = 0; g < groups; g++) { const Fp12<C> p = Fp12<C>::load(part.data() + (size_t)g * sizeof(Fp12<C>)); Fp12<C> t; fp12_mul(&t, &acc, &p); acc = t; }
+            for (int g = 0; g < groups; g++) { const Fp12<C> p = Fp12<C>::load_host(part.data() + (size_t)g * sizeof(Fp12<C>)); Fp12<C> t; fp12_mul(&t, &acc, &p); acc = t; }
         }
-        acc.store(h_out_fp12); return 0;
+        acc.store_host(h_out_fp12); return 0;
     });
 }
 int32_t cg_final_exp_check_batch(cg_ctx* ctx, int32_t curve, const void* h_fp12s, int32_t k, size_t n, const void* h_target_fp12, int32_t* ok) {

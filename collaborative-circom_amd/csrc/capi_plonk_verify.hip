@@ -53,11 +53,17 @@ int32_t cg_plonk_verify_scalars_host(int32_t curve, const void* h_key_points, co
         if (int rc = load_key<C>(key, h_key_points, h_k1, h_k2, h_omega, power, n_pub)) return rc;
         Fr sums[PLONK_N_KEY_SCALARS];
         for (auto& s : sums) s = Fr::zero();
+        // The caller's buffers need only be 8-byte aligned (u64 arrays), Fr and Pt are alignas(16): every proof goes through aligned locals.
+        Pt commits[PLONK_N_COMMITS]; Fr evals[PLONK_N_EVALS], ch[PLONK_N_CHALLENGES], sp[PLONK_N_PROOF_SCALARS], sk[PLONK_N_KEY_SCALARS];
+        std::vector<Fr> pubs(n_pub);
         for (size_t i = 0; i < n; i++) {
-            Fr* sk = (Fr*)h_key_scalars + i * PLONK_N_KEY_SCALARS;
-            h_valid[i] = plonk_verify_scalars<C>(key, (const Pt*)h_commits + i * PLONK_N_COMMITS, (const Fr*)h_evals + i * PLONK_N_EVALS, (const Fr*)h_pubs + i * n_pub,
-                                                 h_coeff128 ? (const uint32_t*)h_coeff128 + 4 * i : nullptr, (Fr*)h_challenges + i * PLONK_N_CHALLENGES,
-                                                 (Fr*)h_proof_scalars + i * PLONK_N_PROOF_SCALARS, sk);
+            memcpy(commits, (const uint8_t*)h_commits + i * sizeof commits, sizeof commits);
+            memcpy(evals, (const uint8_t*)h_evals + i * sizeof evals, sizeof evals);
+            if (n_pub) memcpy(pubs.data(), (const uint8_t*)h_pubs + i * n_pub * sizeof(Fr), n_pub * sizeof(Fr));
+            h_valid[i] = plonk_verify_scalars<C>(key, commits, evals, pubs.data(), h_coeff128 ? (const uint32_t*)h_coeff128 + 4 * i : nullptr, ch, sp, sk);
+            memcpy((uint8_t*)h_challenges + i * sizeof ch, ch, sizeof ch);
+            memcpy((uint8_t*)h_proof_scalars + i * sizeof sp, sp, sizeof sp);
+            memcpy((uint8_t*)h_key_scalars + i * sizeof sk, sk, sizeof sk);
             for (int k = 0; k < PLONK_N_KEY_SCALARS; k++) sums[k] = sums[k] + sk[k];
         }
         memcpy(h_key_sums, sums, sizeof sums);

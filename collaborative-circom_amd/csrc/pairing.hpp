@@ -15,6 +15,7 @@
 // Q must lie in the prime-order subgroup (T never meets +-Q inside the loop then); other inputs give a meaningless value, never a fault.
 // The Fp12 products are out of line and take pointers: an element is 96 (BN254) or 144 (BLS12-381) registers, it lives in scratch either way.
 #pragma once
+#include <cstring>
 #include "curve.hpp"
 #include "pairing_consts.hpp"
 
@@ -47,6 +48,11 @@ struct Fp12 {
     // the ABI's layout: 12 base-field elements, [i][j][k] = c[2j + i].c_k
     CG_HD static Fp12 load(const void* p) { const Fq2* q = (const Fq2*)p; Fp12 r; for (int i = 0; i < 2; i++) for (int j = 0; j < 3; j++) r.c[2 * j + i] = q[i * 3 + j]; return r; }
     CG_HD void store(void* p) const { Fq2* q = (Fq2*)p; for (int i = 0; i < 2; i++) for (int j = 0; j < 3; j++) q[i * 3 + j] = c[2 * j + i]; }
+    // The same for a caller's host buffer, which the ABI only asks to be 8-byte aligned (a u64 array): load and store above cast to Fq2,
+    // alignas(16), and the host compiler turns that into aligned vector moves.  The kernels keep load / store: device buffers are 16-byte
+    // aligned by allocation.
+    static Fp12 load_host(const void* p) { Fq2 q[6]; memcpy(q, p, sizeof q); return load(q); }
+    void store_host(void* p) const { Fq2 q[6]; store(q); memcpy(p, q, sizeof q); }
 };
 // workgroup size of the pairing kernels and the most workgroups (= partial products handed to the host) of the product reduction: shared by
 // the launchers (pairing_impl.hpp) and the caller that sizes the partials' buffer (capi_pairing.hip)

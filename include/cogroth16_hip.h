@@ -441,6 +441,8 @@ int32_t cg_point_generator(int32_t curve, int32_t group, void* h_out);
  * subgroup (cg_point_validate / cg_bases_check_subgroup): for other points the value is meaningless (never a fault).
  * A Miller value is the convention's loop output (conjugated for BLS12-381, whose parameter is negative): Miller values multiply, and
  * the final exponentiation of a product is the product of the pairings.
+ * Alignment: every host buffer of this section and of the Plonk per-proof layer below (points, target-field elements, scalars, exponents)
+ * needs the alignment of a 64-bit word array and no more (8 bytes: a Rust [u64; N], a numpy uint64 view at any element offset).
  *   pairing:        out = e(P, Q).                                                   host arithmetic, no device, no context
  *   final_exp:      out = in^(c (p^12 - 1)/r), c = the convention's factor.         host
  *   fp12_mul / pow: out = a b ; out = a^e, e = exp_limbs64 little-endian 64-bit words.   host (the verifier's O(1) tail)

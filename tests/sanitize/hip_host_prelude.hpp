@@ -1,7 +1,8 @@
-// Force-included in front of lazy_bucket_main.cpp (lazy_bucket.mk): what the device headers under csrc/ need beyond ROCm's own headers to
-// compile as plain C++ for the CPU.  Outside HIP mode <hip/hip_runtime.h> defines __device__, __global__ and friends as empty; the
-// builtins of the kernel BODIES get single-lane stand-ins here so that the headers parse and link.  The host program calls no kernel, only the
-// __device__ functions of lazy29.hpp and msm_kernels.hpp, so none of these is ever executed.
+// Force-included in front of lazy_bucket_main.cpp (lazy_bucket.mk) and pairing_pieces_main.cpp (pairing_pieces.mk): what the device
+// headers under csrc/ need beyond ROCm's own headers to compile as plain C++ for the CPU.  Outside HIP mode <hip/hip_runtime.h> defines
+// __device__, __global__ and friends as empty; the builtins of the kernel BODIES get single-lane stand-ins here so that the headers parse and
+// link.  The host programs call no kernel, only the __device__ functions of lazy29.hpp, msm_kernels.hpp and pairing.hpp, so none of these is
+// ever executed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
