@@ -45,13 +45,16 @@ OPT_MSM_CHUNK, OPT_MSM_WINDOW, OPT_MSM_SCATTER_CAP, OPT_MSM_TABLE_ORDER, OPT_MSM
 OPT_MSM_ONE_STREAM_LOG, OPT_MSM_OFF_MAIN_LOG, OPT_MSM_SOLO_LOG = 10, 11, 12
 # process-wide options (cg_set_option)
 GOPT_SUBGROUP_FULL, GOPT_COMPACT_MIN_LOG, GOPT_SORT_STAGING, GOPT_SORT_SMALL, GOPT_MSM_STAGED_OUT, GOPT_STREAM_PROBES = 1, 2, 3, 4, 5, 6
+# paths of the MSM's scalar-side schedule (cg_msm_schedule_dev: 1 .. 4 can be forced, all five are reported) and the scalar fields' bit lengths
+MSM_PATH_GENERAL, MSM_PATH_SMALL, MSM_PATH_PARTITION, MSM_PATH_DIRECT, MSM_PATH_PARTITION_UNSTAGED = 1, 2, 3, 4, 5
+FR_BITS = {0: 254, 1: 255}
 
 # every symbol include/cogroth16_hip.h declares (checked by tests/test_abi_surface.py)
 ABI_SYMBOLS = [
     "cg_ctx_create", "cg_ctx_create_ex", "cg_ctx_destroy", "cg_ctx_sync", "cg_ctx_stream", "cg_ctx_set_stream", "cg_last_error", "cg_version",
     "cg_dev_alloc", "cg_dev_free", "cg_dev_free_many", "cg_dev_cache_trim", "cg_stream_group_begin", "cg_stream_group_end", "cg_dev_upload", "cg_dev_download", "cg_dev_memset_zero",
     "cg_bases_register", "cg_bases_register_device", "cg_bases_release", "cg_bases_len", "cg_bases_precompute", "cg_bases_check_on_curve", "cg_bases_check_subgroup",
-    "cg_msm", "cg_msm_dev", "cg_msm_dev_begin", "cg_msm_dev_begin_multi", "cg_msm_end", "cg_msm_set_window", "cg_msm_set_chunk", "cg_ctx_set_option", "cg_ctx_get_option", "cg_set_option", "cg_get_option", "cg_msm_scalars_after", "cg_msm_set_scatter_capacity",
+    "cg_msm", "cg_msm_dev", "cg_msm_dev_begin", "cg_msm_dev_begin_multi", "cg_msm_end", "cg_msm_set_window", "cg_msm_set_chunk", "cg_ctx_set_option", "cg_ctx_get_option", "cg_set_option", "cg_get_option", "cg_msm_scalars_after", "cg_msm_set_scatter_capacity", "cg_msm_schedule_dev",
     "cg_ntt", "cg_ntt_dev", "cg_ntt_coset_pair_dev", "cg_chacha12_fr_rand_dev", "cg_chacha12_fr_rand_dev_begin", "cg_chacha12_fr_rand_dev_finish",
     "cg_host_alloc", "cg_host_free", "cg_host_is_pinned", "cg_dev_download_begin", "cg_dev_upload_begin", "cg_stream_mark", "cg_dev_download_begin_after", "cg_copy_wait", "cg_copy_fence",
     "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_shamir_share_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
@@ -443,6 +446,19 @@ class Context:
 
     def set_msm_window(self, c):
         _chk(load().cg_msm_set_window(self.h, int(c)))
+
+    def msm_schedule(self, curve, d_scalars, n, c, shared=False, path=0, cap=0, out=None):
+        """the scalar-side schedule of one device scalar vector (cg_msm_schedule_dev) -> (counts, offsets, sorted, path_taken, overflow);
+        path: 0 = what an MSM call selects, MSM_PATH_* = forced; out: (counts, offsets, sorted) uint32 arrays to fill instead of new ones"""
+        nwin = FR_BITS[curve] // int(c) + 1
+        nbuckets = (1 if shared else nwin) << max(int(c) - 1, 0)
+        if out is None:
+            out = (np.empty(nbuckets, dtype=np.uint32), np.empty(nbuckets, dtype=np.uint32), np.empty(nbuckets * int(cap) if path == MSM_PATH_DIRECT else nwin * int(n), dtype=np.uint32))
+        counts, offsets, sorted_ = out
+        taken, overflow = C.c_int32(0), C.c_uint32(0)
+        _chk(load().cg_msm_schedule_dev(self.h, int(curve), _dp(d_scalars), C.c_size_t(n), int(c), int(bool(shared)), int(path), C.c_uint32(cap), _hp(counts), _hp(offsets), _hp(sorted_),
+                                        C.byref(taken), C.byref(overflow)))
+        return counts, offsets, sorted_, taken.value, overflow.value
 
     # ---- NTT
     def ntt(self, curve, vecs, group_gen, inverse=False, coset_gen=None):

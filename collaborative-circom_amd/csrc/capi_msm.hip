@@ -251,8 +251,8 @@ int msm_begin_multi_impl_(cg_ctx* ctx, int nb, const cg_bases* const* bases, con
             char* sort_scratch = arena_base + (size_t)ss_ * sort_bytes;
             int rc = with_fr(curve, [&](auto tag) -> int {
                 typedef decltype(tag) Fr;
-                return cap ? msm_sort_direct_launch<Fr>(sortst, (const Fr*)d_scalars[j], n, c, nwin, shared ? 1 : 0, cap, sort_scratch, &sps[j], pev)
-                           : msm_sort_launch<Fr>(sortst, (const Fr*)d_scalars[j], n, c, nwin, shared ? 1 : 0, sort_scratch, &sps[j], pev);
+                return cap ? msm_sort_direct_launch<Fr>(sortst, (const Fr*)d_scalars[j], n, c, nwin, shared ? 1 : 0, cap, sort_scratch, sort_bytes, &sps[j], pev)
+                           : msm_sort_launch<Fr>(sortst, (const Fr*)d_scalars[j], n, c, nwin, shared ? 1 : 0, sort_scratch, sort_bytes, &sps[j], pev);
             });
             if (rc) return rc;
             if (cap) for (int b = 0; b < nb; b++) HIPCHK(hipMemcpyAsync(ctx->tickets[slots[b]].h_flags + j, sps[j].overflow, 4, hipMemcpyDeviceToHost, sortst));
@@ -547,6 +547,51 @@ int32_t cg_msm(cg_ctx* ctx, const cg_bases* bases, size_t offset, size_t n, cons
     hipStreamSynchronize(ctx->stream);
     for (int j = 0; j < k; j++) hipFree(d[j]);
     return rc;
+}
+
+// The scalar side alone (see the header): the launchers an MSM call uses, over scratch of the size an MSM call gives them, pre-filled with
+// 0xFF bytes so that what no kernel wrote is recognisable, and the schedule brought down.  Nothing of the context's MSM state is touched.
+int32_t cg_msm_schedule_dev(cg_ctx* ctx, int32_t curve, const void* d_scalars, size_t n, int32_t c, int32_t shared, int32_t path, uint32_t cap,
+                            uint32_t* h_counts, uint32_t* h_offsets, uint32_t* h_sorted, int32_t* path_taken, uint32_t* overflow) {
+    if (!ctx || !d_scalars || !h_counts || !h_offsets || !h_sorted || !path_taken || !overflow) return fail(CG_ERR_ARG, "null argument");
+    if (c < 2 || c > 22) return fail(CG_ERR_ARG, "cg_msm_schedule_dev: window size out of range (2 .. 22)");
+    if (n == 0) return fail(CG_ERR_ARG, "cg_msm_schedule_dev: no scalars");
+    if (shared < 0 || shared > 1 || path < 0 || path > CG_MSM_PATH_DIRECT) return fail(CG_ERR_ARG, "cg_msm_schedule_dev: shared is 0 or 1, path 0 .. 4");
+    int bits = 0;
+    { int rc = with_fr(curve, [&](auto tag) -> int { bits = decltype(tag)::Params::BITS; return 0; }); if (rc) return rc; }
+    const int nwin = bits / c + 1;
+    if (shared && n > ((size_t)1 << 24)) return fail(CG_ERR_ARG, "cg_msm_schedule_dev: one bucket set takes at most 2^24 points (the window shares the entry with the index)");
+    if ((uint64_t)nwin * n >= ((uint64_t)1 << 32)) return fail(CG_ERR_ARG, "cg_msm_schedule_dev: schedule positions are 32-bit");
+    const bool direct = path == CG_MSM_PATH_DIRECT;
+    const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
+    if (direct && (cap < 1 || (uint64_t)nbuckets * cap >= ((uint64_t)1 << 32))) return fail(CG_ERR_ARG, "cg_msm_schedule_dev: the one-pass scatter takes 1 <= cap < 2^32 / buckets");
+    const size_t sorted_len = direct ? nbuckets * cap : (size_t)nwin * n;
+    const size_t bytes = align_up(direct ? msm_sort_direct_scratch_bytes(n, c, nwin, shared, cap) : msm_sort_scratch_bytes(n, c, nwin));   // as msm_begin_multi_impl_ sizes a schedule slot
+    HIPCHK(hipSetDevice(ctx->device));
+    char* scratch = nullptr;
+    HIPCHK(hip_malloc_flush(&scratch, bytes));
+    MsmSortPtrs sp{};
+    uint32_t ov = 0;
+    int rc = [&]() -> int {
+        HIPCHK(hipMemsetAsync(scratch, 0xFF, bytes, ctx->stream));
+        int r = with_fr(curve, [&](auto tag) -> int {
+            typedef decltype(tag) Fr;
+            return direct ? msm_sort_direct_launch<Fr>(ctx->stream, (const Fr*)d_scalars, n, c, nwin, shared, cap, scratch, bytes, &sp, nullptr, path)
+                          : msm_sort_launch<Fr>(ctx->stream, (const Fr*)d_scalars, n, c, nwin, shared, scratch, bytes, &sp, nullptr, path);
+        });
+        if (r) return r;                                     // refused: the host buffers stay as they were
+        HIPCHK(hipMemcpyAsync(h_counts, sp.counts, nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(h_offsets, sp.offsets, nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(h_sorted, sp.sorted, sorted_len * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (sp.overflow) HIPCHK(hipMemcpyAsync(&ov, sp.overflow, 4, hipMemcpyDeviceToHost, ctx->stream));
+        return 0;
+    }();
+    const hipError_t e = hipStreamSynchronize(ctx->stream);
+    (void)hipFree(scratch);
+    if (rc) return rc;
+    HIPCHK(e);
+    *path_taken = sp.path; *overflow = ov;
+    return 0;
 }
 
 }  // extern "C"

@@ -221,12 +221,15 @@ template <class Fr> int launch_bitrev_finish_lazy(hipStream_t st, NttVecs dst, N
 
 // scalar-dependent half of the MSM: digits, histogram, scan, scatter.  Scratch layout and size: msm_sort_scratch_bytes (launchers.hpp).
 // evs (optional, 2 events) bracket the stage.
-inline bool msm_sort_use_partition(size_t n, int c, int nwin, int shared) {
+// any_size: a forced partition sort (cg_msm_schedule_dev) keeps the structural limits and waives the size from which the partition pays
+inline bool msm_sort_use_partition(size_t n, int c, int nwin, int shared, bool any_size = false) {
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
     const size_t nregions = (nbuckets + ((size_t)1 << PART_REGION_LOG) - 1) >> PART_REGION_LOG;
-    return (size_t)nwin * n >= ((size_t)1 << 21) && nregions >= 8 && nregions <= PART_MAX_REGIONS;
+    return (any_size || (size_t)nwin * n >= ((size_t)1 << 21)) && nregions >= 8 && nregions <= PART_MAX_REGIONS;
 }
-template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, char* scratch, MsmSortPtrs* out, hipEvent_t* evs) {
+template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, char* scratch, size_t scratch_bytes, MsmSortPtrs* out, hipEvent_t* evs,
+                                        int force) {
+    if (force != 0 && force != CG_MSM_PATH_GENERAL && force != CG_MSM_PATH_SMALL && force != CG_MSM_PATH_PARTITION) return fail(CG_ERR_ARG, "msm_sort_launch: not a path of the dense schedule");
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
     size_t off = 0;
     auto take = [&](size_t bytes) { void* p = scratch + off; off += align_up(bytes); return p; };
@@ -237,31 +240,44 @@ template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, siz
     uint32_t* offsets = (uint32_t*)take(nbuckets * 4);
     const size_t ntiles = (nbuckets + SCAN_TILE - 1) / SCAN_TILE;
     uint32_t* tile_sums = (uint32_t*)take(ntiles * 4);
-    if (evs) HIPCHK(hipEventRecord(evs[0], st));
+    const size_t entries = (size_t)nwin * n;
     const bool no_small = !global_option(CG_GOPT_SORT_SMALL);                            // cg_set_option: the general six-launch schedule for every size
+    const bool small_fits = shared && nbuckets <= SORT_SMALL_MAX_BUCKETS && entries <= SORT_SMALL_MAX_ENTRIES && n <= (1u << 24);
+    if (force == CG_MSM_PATH_SMALL && (!small_fits || no_small))
+        return fail(CG_ERR_ARG, "the one-workgroup schedule takes one shared bucket set of at most 2^13 buckets and at most 2^15 entries, with CG_GOPT_SORT_SMALL on");
+    if (force == CG_MSM_PATH_PARTITION && !msm_sort_use_partition(n, c, nwin, shared, true)) return fail(CG_ERR_ARG, "the partition sort takes 8 to 4096 regions of 512 buckets");
     // (the kernel asks for up to 68 KiB of dynamic LDS: a device whose workgroups cannot have that — the attribute call fails — takes the general
     // schedule below instead of failing the MSM: ADVICE r5)
     static PerDeviceOnce attr_small; static std::atomic<bool> small_unavailable{false};
-    if (shared && !no_small && !small_unavailable.load(std::memory_order_relaxed) && attr_small.pending()) {
+    const bool may_small = shared && !no_small && (force == 0 || force == CG_MSM_PATH_SMALL);
+    if (may_small && !small_unavailable.load(std::memory_order_relaxed) && attr_small.pending()) {
         if (hipFuncSetAttribute((const void*)k_msm_sort_small<Fr>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((2 * SORT_SMALL_MAX_BUCKETS + 1024) * 4)) == hipSuccess) attr_small.mark();
         else { (void)hipGetLastError(); small_unavailable.store(true); }
     }
-    if (shared && !no_small && !small_unavailable.load(std::memory_order_relaxed) && nbuckets <= SORT_SMALL_MAX_BUCKETS && (size_t)nwin * n <= SORT_SMALL_MAX_ENTRIES && n <= (1u << 24)) {   // small vectors: one launch
+    const bool small = may_small && !small_unavailable.load(std::memory_order_relaxed) && small_fits;
+    if (force == CG_MSM_PATH_SMALL && !small) return fail(CG_ERR_HIP, "the one-workgroup schedule is not available on this device");
+    const bool partition = !small && (force == CG_MSM_PATH_PARTITION || (force == 0 && msm_sort_use_partition(n, c, nwin, shared)));
+    uint64_t* items = nullptr; uint32_t* region_total = nullptr; uint32_t* region_cursor = nullptr; uint32_t* total_items = nullptr;
+    if (partition) {
+        items = (uint64_t*)take(entries * 8);
+        region_total = (uint32_t*)take(PART_MAX_REGIONS * 4);
+        region_cursor = (uint32_t*)take(PART_MAX_REGIONS * 4);
+        total_items = (uint32_t*)take(4);
+    }
+    if (off > scratch_bytes) return fail(CG_ERR_ARG, "msm_sort_launch: the layout of the schedule exceeds its scratch");   // the caller sized it with msm_sort_scratch_bytes
+    if (evs) HIPCHK(hipEventRecord(evs[0], st));
+    if (small) {   // small vectors: one launch
         const size_t lds = (2 * nbuckets + 1024) * 4;
         hipLaunchKernelGGL((k_msm_sort_small<Fr>), dim3(1), dim3(1024), lds, st, d_scalars, (uint32_t)n, c, nwin, counts, offsets, sorted);
         if (evs) HIPCHK(hipEventRecord(evs[1], st));
         HIPCHK(hipGetLastError());
-        out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = 0; out->overflow = nullptr;
+        out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = 0; out->overflow = nullptr; out->path = CG_MSM_PATH_SMALL;
         return 0;
     }
     HIPCHK(hipMemsetAsync(counts, 0, align_up(nbuckets * 4) * 2, st));   // counts + cursors are adjacent
-    if (msm_sort_use_partition(n, c, nwin, shared)) {
-        const size_t entries = (size_t)nwin * n, ptiles = (entries + PART_TILE - 1) / PART_TILE;
+    if (partition) {
+        const size_t ptiles = (entries + PART_TILE - 1) / PART_TILE;
         const uint32_t nregions = (uint32_t)((nbuckets + ((size_t)1 << PART_REGION_LOG) - 1) >> PART_REGION_LOG);
-        uint64_t* items = (uint64_t*)take(entries * 8);
-        uint32_t* region_total = (uint32_t*)take(PART_MAX_REGIONS * 4);
-        uint32_t* region_cursor = (uint32_t*)take(PART_MAX_REGIONS * 4);
-        uint32_t* total_items = (uint32_t*)take(4);
         const unsigned itiles = (unsigned)(((entries + ITEM_TILE - 1) / ITEM_TILE + 7) / 8 * 8);   // a multiple of 8: xcd_tile() deals the tiles to the XCDs
         HIPCHK(hipMemsetAsync(region_total, 0, nregions * 4, st));
         hipLaunchKernelGGL((k_msm_digits_only<Fr>), dim3(grid_for(n)), dim3(256), 0, st, d_scalars, n, c, nwin, digits);
@@ -287,6 +303,7 @@ template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, siz
         if (evs) HIPCHK(hipEventRecord(evs[1], st));
         HIPCHK(hipGetLastError());
         out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = 0; out->overflow = nullptr;
+        out->path = staged && nregions <= STAGE_MAX_REGIONS ? CG_MSM_PATH_PARTITION : CG_MSM_PATH_PARTITION_UNSTAGED;
         return 0;
     }
     hipLaunchKernelGGL((k_msm_digits<Fr>), dim3(grid_for(n)), dim3(256), 0, st, d_scalars, n, c, nwin, shared, digits, counts);
@@ -296,11 +313,14 @@ template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, siz
     hipLaunchKernelGGL(k_msm_scatter, dim3(grid_for((size_t)nwin * n)), dim3(256), 0, st, digits, n, c, nwin, shared, offsets, cursors, sorted);
     if (evs) HIPCHK(hipEventRecord(evs[1], st));
     HIPCHK(hipGetLastError());
-    out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = 0; out->overflow = nullptr;
+    out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = 0; out->overflow = nullptr; out->path = CG_MSM_PATH_GENERAL;
     return 0;
 }
 // optimistic one-pass variant (scratch: msm_sort_direct_scratch_bytes)
-template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, uint32_t cap, char* scratch, MsmSortPtrs* out, hipEvent_t* evs) {
+template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, uint32_t cap, char* scratch, size_t scratch_bytes,
+                                               MsmSortPtrs* out, hipEvent_t* evs, int force) {
+    if (force != 0 && force != CG_MSM_PATH_DIRECT) return fail(CG_ERR_ARG, "msm_sort_direct_launch: the one-pass scatter is the only path here");
+    if (cap < 1) return fail(CG_ERR_ARG, "the one-pass scatter takes a capacity of at least one entry per bucket");
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
     size_t off = 0;
     auto take = [&](size_t bytes) { void* p = scratch + off; off += align_up(bytes); return p; };
@@ -310,6 +330,7 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     const size_t ntiles = (nbuckets + SCAN_TILE - 1) / SCAN_TILE;
     uint32_t* tile_sums = (uint32_t*)take(ntiles * 4);
     uint32_t* overflow = (uint32_t*)take(4);
+    if (off > scratch_bytes) return fail(CG_ERR_ARG, "msm_sort_direct_launch: the layout of the schedule exceeds its scratch");   // the caller sized it with msm_sort_direct_scratch_bytes
     if (evs) HIPCHK(hipEventRecord(evs[0], st));
     HIPCHK(hipMemsetAsync(counts, 0, nbuckets * 4, st));
     HIPCHK(hipMemsetAsync(overflow, 0, 4, st));
@@ -319,7 +340,7 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     hipLaunchKernelGGL(k_scan_tiles, dim3((unsigned)ntiles), dim3(256), 0, st, counts, tile_sums, offsets, nbuckets, cap);
     if (evs) HIPCHK(hipEventRecord(evs[1], st));
     HIPCHK(hipGetLastError());
-    out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = cap; out->overflow = overflow;
+    out->sorted = sorted; out->offsets = offsets; out->counts = counts; out->cap = cap; out->overflow = overflow; out->path = CG_MSM_PATH_DIRECT;
     return 0;
 }
 

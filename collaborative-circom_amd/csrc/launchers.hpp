@@ -25,7 +25,7 @@ constexpr int SCAN_TILE = 2048;         // k_scan_*: counters per workgroup (256
 constexpr int PART_TILE = 16384;        // k_part_*: consecutive (window, scalar) entries per workgroup
 constexpr int PART_REGION_LOG = 9;      // 512 buckets per region
 constexpr int PART_MAX_REGIONS = 4096;  // LDS histogram limit
-struct MsmSortPtrs { const uint32_t* sorted; const uint32_t* offsets; const uint32_t* counts; uint32_t cap; const uint32_t* overflow; };   // cap = 0: dense list
+struct MsmSortPtrs { const uint32_t* sorted; const uint32_t* offsets; const uint32_t* counts; uint32_t cap; const uint32_t* overflow; int path; };   // cap = 0: dense list; path: CG_MSM_PATH_* that ran
 // scratch of msm_sort_launch: digits | sorted | counts | cursors | offsets | tile sums, and on the partition path items | region totals |
 // region cursors | item count.  Sized for the per-window bucket sets (the shared-set mode needs less).
 inline size_t msm_sort_scratch_bytes(size_t n, int c, int nwin) {
@@ -39,8 +39,13 @@ inline size_t msm_sort_direct_scratch_bytes(size_t n, int c, int nwin, int share
     const size_t nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
     return align_up(nbuckets * cap * 4) + 2 * align_up(nbuckets * 4) + align_up(((nbuckets + SCAN_TILE - 1) / SCAN_TILE) * 4) + 256;
 }
-template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, char* scratch, MsmSortPtrs* out, hipEvent_t* evs);
-template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, uint32_t cap, char* scratch, MsmSortPtrs* out, hipEvent_t* evs);
+// scratch_bytes: what the caller allocated; a layout that does not fit is an error, before anything is launched.  force: 0 = the launcher's
+// own choice of path, CG_MSM_PATH_GENERAL / _SMALL / _PARTITION / _DIRECT = that path or an error if its structural limits do not hold
+// (cg_msm_schedule_dev; only the partition sort's performance threshold of 2^21 entries is waived).
+template <class Fr> int msm_sort_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, char* scratch, size_t scratch_bytes, MsmSortPtrs* out, hipEvent_t* evs,
+                                        int force = 0);
+template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scalars, size_t n, int c, int nwin, int shared, uint32_t cap, char* scratch, size_t scratch_bytes,
+                                               MsmSortPtrs* out, hipEvent_t* evs, int force = 0);
 
 // ---- group side of the MSM and the point kernels (msm_impl.hpp)
 template <class F> int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* evs, uint32_t chunk_request, bool g2_slices);

@@ -247,6 +247,22 @@ int32_t cg_msm_set_window(cg_ctx* ctx, int32_t c);
  * cg_msm_end.  cap > 0 forces a capacity (testing).  Measured equally fast on MI355X (the cost is the scattered stores, not the
  * atomics), hence opt-in.  Never changes results. */
 int32_t cg_msm_set_scatter_capacity(cg_ctx* ctx, int32_t cap);
+/* Kernel-level entry (testing, diagnosis): the scalar-side schedule of ONE device scalar vector (n Montgomery-form elements), built by the
+ * launchers an MSM call uses and downloaded.  nwin = BITS / c + 1 windows of c bits (2 <= c <= 22); shared = 1: one bucket set for all windows
+ * (per-window precomputed tables, n <= 2^24), 0: one per window; nbuckets = (shared ? 1 : nwin) * 2^(c-1).
+ *   path   0 = the selection an MSM call with the exact schedule makes; CG_MSM_PATH_GENERAL / _SMALL / _PARTITION / _DIRECT force that path.  A forced
+ *          path keeps its structural limits (small: shared, <= 2^13 buckets, <= 2^15 entries; partition: 8 .. 4096 regions of 512 buckets; direct:
+ *          cap >= 1) — only the 2^21 entries from which the partition sort pays are waived — and is refused otherwise.  CG_GOPT_SORT_SMALL and
+ *          CG_GOPT_SORT_STAGING apply as in an MSM call.
+ *   out    h_counts[nbuckets], h_offsets[nbuckets]; h_sorted: nwin * n entries (dense paths: bucket b owns [offsets[b], offsets[b] + counts[b]); the
+ *          scratch is pre-filled with 0xFF bytes, so positions from the number of non-zero digits on read 0xFFFFFFFF) or nbuckets * cap entries
+ *          (direct: bucket b owns slots [b * cap, b * cap + min(counts[b], cap)), h_counts are the true counts, h_offsets the exclusive scan of
+ *          min(count, cap), *overflow != 0 iff a count exceeds cap).  Entry: bit 31 = negative digit, bits 24-30 = window when shared, low bits = index.
+ *          *path_taken = CG_MSM_PATH_* of what ran (_PARTITION = with LDS-staged scatters).
+ * A refused call (null argument, c, n = 0, n * nwin >= 2^32, limits of a forced path) leaves the host buffers untouched.  Synchronises the stream. */
+enum { CG_MSM_PATH_GENERAL = 1, CG_MSM_PATH_SMALL = 2, CG_MSM_PATH_PARTITION = 3, CG_MSM_PATH_DIRECT = 4, CG_MSM_PATH_PARTITION_UNSTAGED = 5 };
+int32_t cg_msm_schedule_dev(cg_ctx* ctx, int32_t curve, const void* d_scalars, size_t n, int32_t c, int32_t shared, int32_t path, uint32_t cap,
+                            uint32_t* h_counts, uint32_t* h_offsets, uint32_t* h_sorted, int32_t* path_taken, uint32_t* overflow);
 
 /* ---- FFTProvider::{fft,ifft}_in_place  (traits.rs:535-558; rep3.rs:893-921) ------------------------------------
  * k vectors of n = 2^j scalar-field elements, natural order in and out.  `h_group_gen` = domain.group_gen (the caller
