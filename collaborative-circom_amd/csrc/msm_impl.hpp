@@ -9,11 +9,11 @@
 namespace cg {
 
 // buckets per lane of k_msm_bitsum_partial and the resulting workgroups per bit
-template <class B> constexpr int bitsum_items() { return BITSUM_ITEMS; }   // 2 for G2 measured slower (four times the LDS trees): 2^18 step 8.5 -> 10.1 ms
+constexpr int bitsum_items() { return BITSUM_ITEMS; }   // 2 for G2 measured slower (four times the LDS trees): 2^18 step 8.5 -> 10.1 ms
 // TINY bucket sets (<= 2^10 buckets: circuits of a few hundred constraints) take ONE bucket per lane: with 8 a 128-bucket set is summed by 8 lanes in
 // 8 serial additions + 3 tree levels (11 x 22 us for G2), with 1 by 64 lanes in 1 + 6
 inline int bitsum_items_for(uint32_t nb) { return nb <= 1024u ? 1 : BITSUM_ITEMS; }
-template <class B> uint32_t bitsum_groups(uint32_t nb) { const uint32_t it = (uint32_t)bitsum_items_for(nb); return std::max<uint32_t>(1, (nb / 2 + 256 * it - 1) / (256 * it)); }
+inline uint32_t bitsum_groups(uint32_t nb) { const uint32_t it = (uint32_t)bitsum_items_for(nb); return std::max<uint32_t>(1, (nb / 2 + 256 * it - 1) / (256 * it)); }
 
 // coordinates in the base field (G1: VGPR accumulator) or its quadratic extension (G2: LDS accumulator)
 template <class F> struct IsFp2 { static constexpr bool value = false; };
@@ -24,34 +24,33 @@ template <class B> struct IsFp2<Fp2<B>> { static constexpr bool value = true; };
 template <class F> constexpr size_t acc_resident_lanes() { return IsFp2<F>::value ? 0 : (size_t)256 * (sizeof(F) == 32 ? 3 : 2) * 256; }
 
 template <class F>
-size_t msm_acc_scratch_bytes(size_t n, int c, int nwin, bool shared, uint32_t chunk_request) {
-    typedef typename BucketOf<F>::type B;
+MsmGeom msm_geom_of(size_t n, int c, int nwin, bool shared, uint32_t chunk_request) {
     MsmGeom g = msm_geom(n, c, nwin, shared, acc_resident_lanes<F>(), chunk_request, IsFp2<F>::value);
-    g.bit_groups = bitsum_groups<B>(g.nb);
-    return align_up(g.nbuckets * sizeof(B)) + align_up((size_t)g.nchunks * sizeof(B)) + align_up((size_t)g.nchunks * 4) +
-           align_up(std::max({(size_t)g.nsets * g.segs, (size_t)64 * g.bit_groups, g.grid_partials()}) * sizeof(B)) + align_up((size_t)std::max(g.ngroups, 64) * sizeof(XYZZ<F>));
+    g.bit_groups = bitsum_groups(g.nb);
+    return g;
 }
 
-// scratch of one bucket set (one rotating slot of the context's arena): the same layout for every set of a launch geometry
+// scratch of one bucket set (one rotating slot of the context's arena): the same layout for every set of a launch geometry.
+// The layout is stated here alone: msm_acc_scratch_bytes asks for `bytes` with no arena behind it.
 template <class F>
 struct AccScratch {
     typedef typename BucketOf<F>::type B;
     B* buckets; B* cont; uint32_t* cont_bucket; B* partials; XYZZ<F>* wsums;
+    size_t bytes;
     AccScratch(char* scratch, const MsmGeom& g) {
         size_t off = 0;
-        auto take = [&](size_t bytes) { void* p = scratch + off; off += align_up(bytes); return p; };
+        auto take = [&](size_t size) { void* p = scratch ? scratch + off : nullptr; off += align_up(size); return p; };
         buckets = (B*)take(g.nbuckets * sizeof(B));
         cont = (B*)take((size_t)g.nchunks * sizeof(B));
         cont_bucket = (uint32_t*)take((size_t)g.nchunks * 4);
         partials = (B*)take(std::max({(size_t)g.nsets * g.segs, (size_t)64 * g.bit_groups, g.grid_partials()}) * sizeof(B));
         wsums = (XYZZ<F>*)take((size_t)std::max(g.ngroups, 64) * sizeof(XYZZ<F>));
+        bytes = off;
     }
 };
 template <class F>
-MsmGeom msm_geom_of(size_t n, int c, int nwin, bool shared, uint32_t chunk_request) {
-    MsmGeom g = msm_geom(n, c, nwin, shared, acc_resident_lanes<F>(), chunk_request, IsFp2<F>::value);
-    g.bit_groups = bitsum_groups<typename BucketOf<F>::type>(g.nb);
-    return g;
+size_t msm_acc_scratch_bytes(size_t n, int c, int nwin, bool shared, uint32_t chunk_request) {
+    return AccScratch<F>(nullptr, msm_geom_of<F>(n, c, nwin, shared, chunk_request)).bytes;
 }
 
 // Bucket accumulation of UP TO ACC_MAX_SETS (bases, sorted schedule) pairs of one coordinate field and one launch geometry, each into
@@ -62,7 +61,7 @@ template <class F>
 int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* evs, uint32_t chunk_request, bool g2_slices) {
     if (nsets < 1 || nsets > ACC_MAX_SETS) return fail(CG_ERR_ARG, "internal: accumulation batch size");
     const MsmGeom g = msm_geom_of<F>(n, c, nwin, shared, chunk_request);
-    typedef typename BucketOf<F>::type B;                 // limb-form points for the lazy pipelines, saturated XYZZ otherwise
+    typedef typename BucketOf<F>::type B;                 // limb-form points (XYZZL)
     AccSets<F> S{};
     for (int i = 0; i < nsets; i++) {
         const AccScratch<F> sc(sets[i].scratch, g);
@@ -169,13 +168,13 @@ int msm_reduce_batch(hipStream_t st2, const MsmRedSet* sets, int nsets, size_t n
     if (g.bitsum) {
         static PerDeviceOnce attr_set2;
         if (attr_set2.pending()) {
-            HIPCHK(hipFuncSetAttribute((const void*)k_msm_bitsum_partial<B, bitsum_items<B>()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(256 * sizeof(B))));
+            HIPCHK(hipFuncSetAttribute((const void*)k_msm_bitsum_partial<B, bitsum_items()>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(256 * sizeof(B))));
             HIPCHK(hipFuncSetAttribute((const void*)k_msm_bitsum_partial<B, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(256 * sizeof(B))));
             HIPCHK(hipFuncSetAttribute((const void*)k_msm_bitsum_final<F, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(64 * sizeof(B))));
             attr_set2.mark();
         }
         if (bitsum_items_for(g.nb) == 1) hipLaunchKernelGGL((k_msm_bitsum_partial<B, 1>), dim3((unsigned)(c * g.bit_groups), ys), dim3(256), 256 * sizeof(B), st2, S, g.nb, g.bit_groups);
-        else hipLaunchKernelGGL((k_msm_bitsum_partial<B, bitsum_items<B>()>), dim3((unsigned)(c * g.bit_groups), ys), dim3(256), 256 * sizeof(B), st2, S, g.nb, g.bit_groups);
+        else hipLaunchKernelGGL((k_msm_bitsum_partial<B, bitsum_items()>), dim3((unsigned)(c * g.bit_groups), ys), dim3(256), 256 * sizeof(B), st2, S, g.nb, g.bit_groups);
         hipLaunchKernelGGL((k_msm_bitsum_final<F, B>), dim3((unsigned)c, ys), dim3(64), 64 * sizeof(B), st2, S, g.bit_groups);
         return deliver((size_t)c);
     }

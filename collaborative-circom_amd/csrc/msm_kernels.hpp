@@ -1,20 +1,26 @@
 // Variable-base multi-scalar multiplication (Pippenger bucket method) for gfx950, G1 and G2.
 // Replaces `C::msm_unchecked(points, scalars)` of ark-ec 0.4.2 as called from
-// `/root/reference/mpc-core/src/protocols/rep3.rs:942-943` (shamir.rs:1035, plain.rs:414).  The result is the same group
+// the reference's `mpc-core/src/protocols/rep3.rs:942-943` (shamir.rs:1035, plain.rs:414).  The result is the same group
 // element; which window size / bucket order is used cannot change it.
 //
-// Pipeline (all on one HIP stream, no host round trip until the per-window sums come back):
+// Pipeline (no host round trip until the sums come back; steps 1-3 are in msm_sort_kernels.hpp):
 //   1. k_msm_digits      scalars: Montgomery -> canonical, signed c-bit digits (buckets 1..2^(c-1)), per-(window,bucket)
 //                        histogram with global atomics.                                   [reads 32 B/scalar]
 //   2. k_scan_exclusive  bucket offsets.
 //   3. k_msm_scatter     counting sort of point indices by (window, bucket).
-//   4. k_msm_accumulate  one lane per CHUNK of 128 consecutive sorted entries (balanced work per lane whatever the bucket sizes):
-//                        gather the points (64/128 B each) and fold them with XYZZ mixed additions (8M+2S); pieces of a bucket
-//                        that straddle chunks are merged by k_msm_merge_cont.  This is where the time goes: integer VALU bound.
-//   5. k_msm_reduce_segments / k_msm_window_sum   running-sum bucket reduction, split into 2^15/L independent segments per
-//                        window (segment result = sum (b-lo+1) B_b + lo * sum B_b), then a per-window tree sum in LDS.
-//   6. host: Horner fold of the <= 64 window sums (c doublings each) — O(1) work, kept on the host.
+//   4. k_msm_accumulate_pf (compact lists) / k_msm_accumulate (padded lists)   one lane per CHUNK of consecutive sorted entries
+//                        (balanced work per lane whatever the bucket sizes): gather the points (64/128 B each) and fold them with
+//                        XYZZ mixed additions (8M+2S) on signed lazy limbs (lazy29.hpp), the accumulator in VGPRs (G1) or LDS (G2).
+//                        This is where the time goes: integer VALU bound.  Buckets are written in limb form (XYZZL) and stay in it.
+//   5. k_msm_merge_*     the pieces of a bucket that straddle chunks are added into it.
+//   6. bucket reduction, one of three kinds by the size of the bucket set, each ending in canonical XYZZ sums for the host:
+//        k_msm_reduce_segments / k_msm_window_sum   running sums over 2^15/L independent segments per window (segment result =
+//                        sum (b-lo+1) B_b + lo * sum B_b), then a per-window tree sum in LDS;
+//        k_msm_bitsum_*  small sets: one plain tree sum per bit of the bucket weight;
+//        k_msm_grid_*    large shared sets: row and column sums of the bucket grid, then sums by bits.
+//   7. host: Horner fold of the <= 64 window or bit sums — O(1) work, kept on the host.
 // With uniformly random scalars (REP3 shares always are) every bucket receives n/2^(c-1) +- sqrt points: lanes are balanced.
+// The tables' points, the accumulators and the buckets are the only forms: Affine<F> in, XYZZL<F> throughout, XYZZ<F> out.
 #pragma once
 #include <type_traits>
 #include "common.hpp"
@@ -40,64 +46,6 @@ __device__ __forceinline__ void st_struct(A* p, const A& r) {
     uint4* q = reinterpret_cast<uint4*>(p);
     const uint4* d = reinterpret_cast<const uint4*>(&r);
     _Pragma("unroll") for (int i = 0; i < (int)(sizeof(A) / 16); i++) q[i] = d[i];
-}
-
-// Accumulator storage policy of the bucket-accumulation kernel.
-//  * RegAcc: the XYZZ accumulator lives in VGPRs (G1: 32 dwords, 3 waves/SIMD).
-//  * LdsAcc: the accumulator lives in LDS, one 16-byte column per lane (G2: 64..96 dwords per lane would otherwise push the
-//    kernel to 1 wave/SIMD; in LDS it costs ~32 ds_read/ds_write_b128 per mixed addition, nothing next to ~13k VALU ops).
-template <class F>
-struct RegAcc {
-    typedef uint4 LdsT;
-    XYZZ<F> v;
-    bool inf;
-    __device__ __forceinline__ void init(uint4*, int, int) { inf = true; }
-    __device__ __forceinline__ F get(int f) const { return f == 0 ? v.x : f == 1 ? v.y : f == 2 ? v.zz : v.zzz; }
-    __device__ __forceinline__ void set(int f, const F& x) { if (f == 0) v.x = x; else if (f == 1) v.y = x; else if (f == 2) v.zz = x; else v.zzz = x; }
-};
-template <class F>
-struct LdsAcc {
-    typedef uint4 LdsT;
-    static constexpr int Q = sizeof(F) / 16;          // 16-byte quads per coordinate
-    uint4* base; int stride;                           // quad e of this lane at base[e * stride]
-    bool inf;
-    __device__ __forceinline__ void init(uint4* lds, int tid, int nthreads) { base = lds + tid; stride = nthreads; inf = true; }
-    __device__ __forceinline__ F get(int f) const {
-        F r; uint4* d = reinterpret_cast<uint4*>(&r);
-        _Pragma("unroll") for (int i = 0; i < Q; i++) d[i] = base[(f * Q + i) * stride];
-        return r;
-    }
-    __device__ __forceinline__ void set(int f, const F& x) {
-        const uint4* d = reinterpret_cast<const uint4*>(&x);
-        _Pragma("unroll") for (int i = 0; i < Q; i++) base[(f * Q + i) * stride] = d[i];
-    }
-};
-
-// acc += (x2, y2), formulas of xyzz_madd scheduled so that each accumulator coordinate is fetched right before its use
-template <class F, class Acc>
-__device__ __forceinline__ void acc_madd(Acc& acc, const F& x2, const F& y2) {
-    if (acc.inf) { acc.set(0, x2); acc.set(1, y2); acc.set(2, F::one()); acc.set(3, F::one()); acc.inf = false; return; }
-    F P = x2 * acc.get(2) - acc.get(0);
-    F R = y2 * acc.get(3) - acc.get(1);
-    if (P.is_zero()) {
-        if (R.is_zero()) { XYZZ<F> d = xyzz_dbl_affine(x2, y2); acc.inf = d.is_inf(); acc.set(0, d.x); acc.set(1, d.y); acc.set(2, d.zz); acc.set(3, d.zzz); }
-        else acc.inf = true;
-        return;
-    }
-    F PP = P.sqr();
-    acc.set(2, acc.get(2) * PP);
-    F PPP = P * PP;
-    acc.set(3, acc.get(3) * PPP);
-    F Q = acc.get(0) * PP;
-    F X3 = R.sqr() - PPP - Q.dbl();
-    acc.set(0, X3);
-    acc.set(1, R * (Q - X3) - acc.get(1) * PPP);
-}
-template <class F, class Acc>
-__device__ __forceinline__ void acc_flush(Acc& acc, XYZZ<F>* dst) {
-    XYZZ<F> r = acc.inf ? XYZZ<F>::infinity() : XYZZ<F>{acc.get(0), acc.get(1), acc.get(2), acc.get(3)};
-    st_struct(dst, r);
-    acc.inf = true;
 }
 
 // Fp2 = Fp[u]/(u^2+1) on lazy limbs.  Products are accumulated FUSED: c0 = a0 b0 - a1 b1 and c1 = a0 b1 + a1 b0 are each one
@@ -162,7 +110,10 @@ template <class B> struct LazyOf<Fp2<B>> { typedef L29x2<Fp2<B>> type; };
 template <class L> struct LazyShift { static constexpr int value = L::SH; };                 // bits between the ABI's and the lazy Montgomery domain
 template <class F2> struct LazyShift<L29x2<F2>> { static constexpr int value = L29x2<F2>::L::SH; };
 
-// lazy accumulator in VGPRs (G1) or LDS (G2: 72 dwords per lane)
+// Accumulator storage policy of the bucket-accumulation kernels: four lazy coordinates and an infinity flag.
+//  * RegAcc29: the accumulator lives in VGPRs (G1).
+//  * LdsAcc29: the accumulator lives in LDS, one dword column per lane (G2: 72 / 112 dwords per lane, which in registers would push
+//    the kernel to one wave per SIMD; the LDS traffic of a mixed addition is nothing next to its ~13k VALU ops).
 template <class F>
 struct RegAcc29 {
     typedef uint32_t LdsT;
@@ -190,23 +141,17 @@ struct LdsAcc29 {
         _Pragma("unroll") for (int i = 0; i < W; i++) base[(f * W + i) * stride] = d[i];
     }
 };
-template <class Acc> struct IsLazyAcc { static constexpr bool value = false; };
-template <class F> struct IsLazyAcc<RegAcc29<F>> { static constexpr bool value = true; };
-template <class F> struct IsLazyAcc<LdsAcc29<F>> { static constexpr bool value = true; };
 
-// Buckets, continuation pieces and reduction partials of the lazy pipelines stay in LIMB form (XYZZL: 4 lazy coordinates;
-// all limbs of ZZ zero = infinity, which a finite point can never show because its ZZ is non-zero modulo p), so nothing is
-// converted between the accumulation and the final per-window sums.  Saturated XYZZ<F> is kept for fields without a lazy form.
+// Buckets, continuation pieces and reduction partials stay in LIMB form (XYZZL: 4 lazy coordinates; all limbs of ZZ zero =
+// infinity, which a finite point can never show because its ZZ is non-zero modulo p), so nothing is converted between the
+// accumulation and the final per-window sums, which leave as saturated XYZZ<F> for the host (bk_to_xyzz).
 template <class F>
 struct alignas(16) XYZZL {
     typedef typename LazyOf<F>::type L;
     L c[4];   // X, Y, ZZ, ZZZ
 };
-template <class F> struct BucketOf { typedef XYZZ<F> type; };
-template <class P> struct BucketOf<Fp<P>> { typedef XYZZL<Fp<P>> type; };                  // every field has a lazy form (9 x 29 or 14 x 28 limbs)
-template <class B> struct BucketOf<Fp2<B>> { typedef XYZZL<Fp2<B>> type; };
+template <class F> struct BucketOf { typedef XYZZL<F> type; };                            // every field has a lazy form (9 x 29 or 14 x 28 limbs)
 
-template <class F> __device__ __forceinline__ bool bk_is_inf(const XYZZ<F>& p) { return p.is_inf(); }
 template <class F> __device__ __forceinline__ bool bk_is_inf(const XYZZL<F>& p) {
     const int32_t* w = reinterpret_cast<const int32_t*>(&p.c[2]); int32_t o = 0;
     _Pragma("unroll") for (int i = 0; i < (int)(sizeof(p.c[2]) / 4); i++) o |= w[i];
@@ -240,7 +185,8 @@ template <class F> __device__ __attribute__((noinline)) XYZZL<F> bk_dbl(const XY
 // (Round 6 measured the column form of acc_madd_lazy_cols for this full addition as well — groups of three independent chains, no wait states: the
 // merge / reduction kernels go from 138-149 to 176-179 VGPRs and get no faster: reduce stage of a 2^22 G1 set 0.427-0.431 -> 0.438-0.454 ms, BLS12-381
 // 0.770 -> 0.87; profiles/r06_acc_cols_ab.txt.  Row form kept.)
-template <class F>
+// INL = false is the body of the out-of-line bk_add below: the same addition with its doubling branch a call as well.
+template <bool INL = true, class F>
 __device__ __forceinline__ XYZZL<F> bk_add_inl(const XYZZL<F>& a, const XYZZL<F>& b) {
     typedef typename LazyOf<F>::type L;
     if (bk_is_inf(a)) return b;
@@ -248,7 +194,7 @@ __device__ __forceinline__ XYZZL<F> bk_add_inl(const XYZZL<F>& a, const XYZZL<F>
     L U1 = L::mul(a.c[0], b.c[2]), S1 = L::mul(a.c[1], b.c[3]);
     L P = L::mul(b.c[0], a.c[2]) - U1, R = L::mul(b.c[1], a.c[3]) - S1;
     if (L::is_zero_mod_p(P.norm())) {
-        if (L::is_zero_mod_p(R.norm())) return bk_dbl_inl(a);
+        if (L::is_zero_mod_p(R.norm())) { if constexpr (INL) return bk_dbl_inl(a); else return bk_dbl(a); }
         return bk_inf<XYZZL<F>>();
     }
     L PP = L::sqr(P), PPP = L::mul(P, PP), Q = L::mul(U1, PP);
@@ -260,30 +206,7 @@ __device__ __forceinline__ XYZZL<F> bk_add_inl(const XYZZL<F>& a, const XYZZL<F>
     r.c[3] = L::mul(L::mul(a.c[3], b.c[3]), PPP);
     return r;
 }
-template <class F> __device__ __forceinline__ XYZZ<F> bk_add_inl(const XYZZ<F>& a, const XYZZ<F>& b) { return xyzz_add(a, b); }
-template <class F>
-__device__ __attribute__((noinline)) XYZZL<F> bk_add(const XYZZL<F>& a, const XYZZL<F>& b) {
-    typedef typename LazyOf<F>::type L;
-    if (bk_is_inf(a)) return b;
-    if (bk_is_inf(b)) return a;
-    L U1 = L::mul(a.c[0], b.c[2]), S1 = L::mul(a.c[1], b.c[3]);
-    L P = L::mul(b.c[0], a.c[2]) - U1, R = L::mul(b.c[1], a.c[3]) - S1;
-    if (L::is_zero_mod_p(P.norm())) {
-        if (L::is_zero_mod_p(R.norm())) return bk_dbl(a);
-        return bk_inf<XYZZL<F>>();
-    }
-    L PP = L::sqr(P), PPP = L::mul(P, PP), Q = L::mul(U1, PP);
-    L X3 = (L::sqr(R) - PPP - Q.dbl()).norm();
-    XYZZL<F> r;
-    r.c[0] = X3;
-    r.c[1] = L::mul_sub(R, Q - X3, S1, PPP);
-    r.c[2] = L::mul(L::mul(a.c[2], b.c[2]), PP);
-    r.c[3] = L::mul(L::mul(a.c[3], b.c[3]), PPP);
-    return r;
-}
-template <class F> __device__ __forceinline__ XYZZ<F> bk_add(const XYZZ<F>& a, const XYZZ<F>& b) { return xyzz_add(a, b); }
-template <class F> __device__ __forceinline__ XYZZ<F> bk_dbl(const XYZZ<F>& a) { return xyzz_dbl(a); }
-template <class F> __device__ __forceinline__ XYZZ<F> bk_to_xyzz(const XYZZ<F>& a) { return a; }
+template <class F> __device__ __attribute__((noinline)) XYZZL<F> bk_add(const XYZZL<F>& a, const XYZZL<F>& b) { return bk_add_inl<false>(a, b); }
 template <class F> __device__ __forceinline__ XYZZ<F> bk_to_xyzz(const XYZZL<F>& a) {
     typedef typename LazyOf<F>::type L;
     if (bk_is_inf(a)) return XYZZ<F>::infinity();
@@ -298,25 +221,28 @@ template <class F> __device__ __forceinline__ XYZZ<F> bk_to_xyzz(const XYZZL<F>&
 // fall into four groups of independent ones — (U2, S2), (P^2, R^2), (P PP, X PP, ZZ PP), (ZZZ PPP, R (Q - X3) - Y PPP).
 template <class L> struct HasColEngine { static constexpr bool value = false; };
 template <class F> struct HasColEngine<L29<F>> { static constexpr bool value = true; };
+// The branch of the mixed addition taken when the incoming point has the accumulator's x (P = 0 modulo p; rare): the sum is the point's
+// doubling (same y, R = 0 as well) or the point at infinity (cancellation).
+template <class F, class Acc, class L>
+__device__ __forceinline__ void acc_madd_same_x(Acc& acc, const F& x2f, const F& y2f, const L& R, bool negate) {
+    if (L::is_zero_mod_p(R.norm())) {
+        XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
+        acc.inf = d.is_inf();
+        if (!acc.inf) {
+            const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
+            constexpr int SH = LazyShift<L>::value;
+            acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
+            acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
+        }
+    } else acc.inf = true;
+}
 template <class F, class Acc, class L>
 __device__ __forceinline__ void acc_madd_lazy_cols(Acc& acc, const F& x2f, const F& y2f, const L& x2, const L& y2, bool negate) {
     const L X = acc.get(0), Y = acc.get(1), ZZ = acc.get(2), ZZZ = acc.get(3);
     typename L::ColMul u2(x2, ZZ), s2(y2, ZZZ);
     L::run_cols(u2, s2);
     const L P = u2.r - X, R = s2.r - Y;
-    if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) {   // same x: doubling or cancellation (rare)
-        if (L::is_zero_mod_p(R.norm())) {
-            XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
-            acc.inf = d.is_inf();
-            if (!acc.inf) {
-                const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
-                constexpr int SH = LazyShift<L>::value;
-                acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
-                acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
-            }
-        } else acc.inf = true;
-        return;
-    }
+    if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) { acc_madd_same_x(acc, x2f, y2f, R, negate); return; }
     typename L::ColSqr pp(P), rr(R);
     L::run_cols(pp, rr);
     typename L::ColMul ppp(P, pp.r), q(X, pp.r), zz(ZZ, pp.r);
@@ -338,19 +264,7 @@ __device__ __forceinline__ void acc_madd_lazy_cols(Acc& acc, const F& x2f, const
     auto sqr = [](const L& a) { typename L::Col2Sqr c(a); L1::run_cols(c.c0, c.c1); return c.res(); };
     const L P = mul(x2, acc.get(2)) - acc.get(0);
     const L R = mul(y2, acc.get(3)) - acc.get(1);
-    if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) {   // same x: doubling or cancellation (rare)
-        if (L::is_zero_mod_p(R.norm())) {
-            XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
-            acc.inf = d.is_inf();
-            if (!acc.inf) {
-                const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
-                constexpr int SH = LazyShift<L>::value;
-                acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
-                acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
-            }
-        } else acc.inf = true;
-        return;
-    }
+    if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) { acc_madd_same_x(acc, x2f, y2f, R, negate); return; }
     const L PP = sqr(P);
     const L PPP = mul(P, PP);
     const L Q = mul(acc.get(0), PP);
@@ -378,19 +292,7 @@ __device__ __forceinline__ void acc_madd_lazy(Acc& acc, const F& x2f, const F& y
     if constexpr (HasColEngine<L>::value) { acc_madd_lazy_cols<F>(acc, x2f, y2f, x2, y2, negate); return; }   // products by columns; the row form below serves the rest (BLS12-381 G2)
     L P = L::mul(x2, acc.get(2)) - acc.get(0);
     L R = L::mul(y2, acc.get(3)) - acc.get(1);
-    if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) {   // same x: doubling or cancellation (rare)
-        if (L::is_zero_mod_p(R.norm())) {
-            XYZZ<F> d = L::dbl_affine(x2f, negate ? y2f.neg() : y2f);
-            acc.inf = d.is_inf();
-            if (!acc.inf) {
-                const L one = L::one_small();                 // in [0, p): the products below stay in (0, 1.2 p) (L::one() is about 19 p on BLS12-381 Fq)
-                constexpr int SH = LazyShift<L>::value;
-                acc.set(0, L::mul(L::template unpack<SH>(d.x), one)); acc.set(1, L::mul(L::template unpack<SH>(d.y), one));
-                acc.set(2, L::mul(L::template unpack<SH>(d.zz), one)); acc.set(3, L::mul(L::template unpack<SH>(d.zzz), one));
-            }
-        } else acc.inf = true;
-        return;
-    }
+    if (L::maybe_zero_mod_p(P) && L::is_zero_mod_p(P.norm())) { acc_madd_same_x(acc, x2f, y2f, R, negate); return; }
     L PP = L::sqr(P);
     L PPP = L::mul(P, PP);
     L Q = L::mul(acc.get(0), PP);
@@ -407,17 +309,12 @@ __device__ __forceinline__ void acc_flush_lazy(Acc& acc, XYZZL<F>* dst) {
     st_struct(dst, r);
     acc.inf = true;
 }
-// dispatch on the accumulator kind
+// The kernels' two entry points.  Kept as a call level of their own although they only forward: without it BN254 G2's accumulation kernels compile to
+// other code (k_msm_accumulate_pf 13673 -> 13659 instructions, the same registers and scratch), and those kernels keep the text they were measured with.
 template <class F, class Acc>
-__device__ __forceinline__ void acc_madd(Acc& acc, const F& x2, const F& y2, bool negate) {
-    if constexpr (IsLazyAcc<Acc>::value) acc_madd_lazy<F>(acc, x2, y2, negate);
-    else acc_madd(acc, x2, negate ? y2.neg() : y2);
-}
-template <class F, class Acc, class B>
-__device__ __forceinline__ void acc_store(Acc& acc, B* dst) {
-    if constexpr (IsLazyAcc<Acc>::value) acc_flush_lazy<F>(acc, dst);
-    else acc_flush(acc, dst);
-}
+__device__ __forceinline__ void acc_madd(Acc& acc, const F& x2, const F& y2, bool negate) { acc_madd_lazy<F>(acc, x2, y2, negate); }
+template <class F, class Acc>
+__device__ __forceinline__ void acc_store(Acc& acc, XYZZL<F>* dst) { acc_flush_lazy<F>(acc, dst); }
 
 // Bucket accumulation, chunk-balanced: lane q folds the L consecutive entries sorted[q*L, (q+1)*L) of the (window, bucket)-
 // sorted index list, whatever buckets they belong to, so every lane of a wave does the same number of mixed additions
