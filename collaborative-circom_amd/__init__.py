@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_shamir_share_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
     "cg_spmv_csr_dev", "cg_r1cs_check_dev", "cg_qap_columns_dev", "cg_plonk_gates_count_dev", "cg_plonk_gates_emit_dev", "cg_plonk_sigma_labels_dev", "cg_vec_mul", "cg_vec_rep3_mul_local",
     "cg_plonk_additions_dev", "cg_plonk_r2_factors_dev", "cg_plonk_r3_blind_dev", "cg_plonk_r3_perm_dev", "cg_plonk_r3_gate_dev", "cg_plonk_mul4_tail_dev", "cg_plonk_r3_t_dev", "cg_plonk_r3_divide_dev",
+    "cg_plonk_gate_check_dev", "cg_vec_mismatch_dev",
     "cg_point_add", "cg_point_neg", "cg_point_scalar_mul", "cg_fixed_base_create", "cg_fixed_base_mul", "cg_fixed_base_destroy", "cg_point_to_affine", "cg_point_from_affine", "cg_point_validate", "cg_fr_is_canonical", "cg_vec_check_canonical_dev", "cg_fr_op",
     "cg_fr_from_canonical", "cg_fr_to_canonical", "cg_fq_to_canonical", "cg_fq_from_canonical", "cg_point_generator",
     "cg_pairing", "cg_final_exp", "cg_fp12_mul", "cg_fp12_pow", "cg_miller_loop", "cg_pairing_check", "cg_miller_batch", "cg_miller_product", "cg_final_exp_check_batch",
@@ -592,6 +593,18 @@ class Context:
         _chk(load().cg_plonk_sigma_labels_dev(self.h, curve, _dp(prev), _dp(omega_powers), C.c_size_t(domain_size), _hp(np.ascontiguousarray(k1, dtype=np.uint64)),
                                               _hp(np.ascontiguousarray(k2, dtype=np.uint64)), _dp(sigma)))
 
+    def plonk_gate_check(self, curve, maps, n_constraints, q, q_stride, domain_size, pub, n_public, ext, n_wires, result):
+        """cg_plonk_gate_check_dev: maps = 3 device buffers of n_constraints u32 (a, b, c), q = 5 device vectors (qm, ql, qr, qo, qc) read at
+        i * q_stride, pub = n_public + 1 elements (entry 0 zero), ext = the extended witness of the wires beyond them; result = 16-byte device
+        buffer (count, first failing row)"""
+        _chk(load().cg_plonk_gate_check_dev(self.h, curve, _ptr_list(maps), C.c_size_t(n_constraints), _ptr_list(q), C.c_size_t(q_stride), C.c_size_t(domain_size),
+                                            _dp(pub), C.c_uint32(n_public), _dp(ext), C.c_size_t(n_wires), _dp(result)))
+
+    def vec_mismatch(self, curve, a, b, n, result, a_stride=1, b_stride=1, first=0):
+        """cg_vec_mismatch_dev: the positions first <= i < n with a[i * a_stride] != b[i * b_stride] (b None: != 0); result = 16-byte device buffer
+        (count, first differing position)"""
+        _chk(load().cg_vec_mismatch_dev(self.h, curve, _dp(a), C.c_size_t(a_stride), _dp(b), C.c_size_t(b_stride), C.c_size_t(first), C.c_size_t(n), _dp(result)))
+
     def spmv_csr(self, curve, row_ptr, col, coeff, n_rows, pub, n_inputs, party, wit_a, wit_b, out_a, out_b):
         _chk(load().cg_spmv_csr_dev(self.h, curve, _dp(row_ptr), _dp(col), _dp(coeff), C.c_size_t(n_rows), _dp(pub), C.c_uint32(n_inputs), int(party),
                                     _dp(wit_a), _dp(wit_b), _dp(out_a), _dp(out_b)))
@@ -964,6 +977,21 @@ class R1cs:
         out = (C.c_size_t * 4)()
         _hchk(load_host().cgh_r1cs_plonk_info(int(device), self.h, out))
         return dict(zip(("n_additions", "n_constraints", "n_vars", "domain_size"), [int(x) for x in out]))
+
+
+    def plonk_gate_origin(self, row, device=0):
+        """where gate row `row` of this circuit's Plonk key comes from (cgh_r1cs_plonk_gate_origin): (kind, R1CS row, index of the addition
+        within that row), kind one of PLONK_GATE_PUBLIC / _ADDITION / _CONSTRAINT / _PADDING, None where a field does not apply"""
+        out = (C.c_uint64 * 3)()
+        _hchk(load_host().cgh_r1cs_plonk_gate_origin(int(device), self.h, C.c_uint64(row), out))
+        return int(out[0]), (None if out[1] == NO_ROW else int(out[1])), (None if out[2] == NO_ROW else int(out[2]))
+
+
+PLONK_GATE_PUBLIC, PLONK_GATE_ADDITION, PLONK_GATE_CONSTRAINT, PLONK_GATE_PADDING = 0, 1, 2, 3
+# the checks of PlonkSession.audit (CGH_PLONK_AUDIT_*), one bit each, in the order of the detail pairs
+PLONK_AUDIT_HEADER, PLONK_AUDIT_BLOCKS, PLONK_AUDIT_ROWS, PLONK_AUDIT_SIGMA, PLONK_AUDIT_COMMITMENTS, PLONK_AUDIT_SRS, PLONK_AUDIT_CIRCUIT = 1, 2, 4, 8, 16, 32, 64
+PLONK_AUDIT_NAMES = ("HEADER", "BLOCKS", "ROWS", "SIGMA", "COMMITMENTS", "SRS", "CIRCUIT")
+PLONK_AUDIT_STAGES = ("header", "transforms", "comparisons", "msm_commitments", "msm_srs", "pairing", "circuit")
 
 
 def setup_groth16(r1cs, seed, zkey_path, device=0):
@@ -1518,6 +1546,29 @@ class PlonkSession:
         ok = C.c_int32(0)
         _hchk(load_host().cgh_plonk_session_verify(self.h, _hp(commits), _hp(evals), _hp(pub), C.byref(ok)))
         return bool(ok.value)
+
+    def check_witness(self, full_witness):
+        """(n_bad, first_bad) of the plain full witness against every row of the key (cgh_plonk_session_check_witness): the number of gate
+        rows it breaks and the smallest one, NO_ROW when it satisfies the key.  No proof is made."""
+        i = self.info
+        w = self._rows("full_witness", full_witness, i["n_vars"] - i["n_additions"])
+        n_bad, first = C.c_uint64(0), C.c_uint64(0)
+        _hchk(load_host().cgh_plonk_session_check_witness(self.h, _hp(w), C.byref(n_bad), C.byref(first)))
+        return int(n_bad.value), int(first.value)
+
+    def audit(self, r1cs=None, seed=None, timing=False):
+        """is the key what `plonk setup` writes (cgh_plonk_session_audit)?  -> (failed, detail): failed = PLONK_AUDIT_* bits, detail = one
+        (which, index) pair per check in the order of PLONK_AUDIT_NAMES, (None, None) for a check that passed.  r1cs: an R1cs to audit the
+        key against its circuit as well; seed: 32 bytes for the SRS check's coefficients (None = OS entropy).  timing=True: also the
+        seconds of PLONK_AUDIT_STAGES"""
+        failed = C.c_uint32(0)
+        det = (C.c_uint64 * (2 * len(PLONK_AUDIT_NAMES)))()
+        sec = (C.c_double * len(PLONK_AUDIT_STAGES))()
+        sd = None if seed is None else (C.c_uint8 * 32).from_buffer_copy(bytes(seed))
+        _hchk(load_host().cgh_plonk_session_audit_timed(self.h, None if r1cs is None else r1cs.h, sd, C.byref(failed), det, sec))
+        opt = lambda v: None if v == NO_ROW else int(v)
+        detail = [(opt(det[2 * k]), opt(det[2 * k + 1])) for k in range(len(PLONK_AUDIT_NAMES))]
+        return (int(failed.value), detail, dict(zip(PLONK_AUDIT_STAGES, sec))) if timing else (int(failed.value), detail)
 
     def prove_rep3_party(self, pub, wit_a, wit_b, net_table, rand_table, blind_a=None, blind_b=None, streams_table=None):
         """ONE REP3 party through the callback ABI (cgh_plonk_session_prove_rep3_party); blind_a/blind_b None = drawn with rand() first.

@@ -686,6 +686,34 @@ int32_t cg_plonk_r3_divide_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, 
         return launch_plonk_r3_divide<Fr>(ctx->stream, g, n);
     });
 }
+int32_t cg_plonk_gate_check_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_maps, size_t n_constraints, const void* const* d_q, size_t q_stride, size_t domain_size,
+                                const void* d_pub, uint32_t n_public, const void* d_ext, size_t n_wires, void* d_result) {
+    if (!ctx || !d_q || !d_pub || !d_result || (n_constraints && !d_maps)) return fail(CG_ERR_ARG, "null argument");
+    if (n_constraints > domain_size) return fail(CG_ERR_ARG, "cg_plonk_gate_check_dev: more gates than rows");
+    if (!q_stride) return fail(CG_ERR_ARG, "cg_plonk_gate_check_dev: the selector stride must be at least 1");
+    if (n_public > domain_size || (size_t)n_public + 1 > n_wires || (n_wires >> 32)) return fail(CG_ERR_ARG, "cg_plonk_gate_check_dev: the public inputs must fit the rows, wire 0 and they the wires, the wires 32 bits");
+    if (n_wires > (size_t)n_public + 1 && !d_ext) return fail(CG_ERR_ARG, "cg_plonk_gate_check_dev: wires beyond the public ones need the extended witness");
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        PlonkCheckArgs<Fr> g; memset(&g, 0, sizeof g);
+        for (int w = 0; w < 3; w++) { g.map[w] = n_constraints ? d_maps[w] : nullptr; if (n_constraints && !g.map[w]) return fail(CG_ERR_ARG, "null map"); }
+        for (int t = 0; t < 5; t++) { g.q[t] = (const Fr*)d_q[t]; if (!g.q[t]) return fail(CG_ERR_ARG, "null selector vector"); }
+        g.q_stride = q_stride; g.n_constraints = n_constraints; g.pub = (const Fr*)d_pub; g.n_public = n_public; g.ext = (const Fr*)d_ext; g.n_wires = (uint32_t)n_wires;
+        StatScope ss(ctx, TAG_VEC);
+        return launch_plonk_gate_check<Fr>(ctx->stream, g, domain_size, (unsigned long long*)d_result);
+    });
+}
+int32_t cg_vec_mismatch_dev(cg_ctx* ctx, int32_t curve, const void* d_a, size_t a_stride, const void* d_b, size_t b_stride, size_t first, size_t n, void* d_result) {
+    if (!ctx || !d_result || (first < n && !d_a)) return fail(CG_ERR_ARG, "null argument");
+    if (!a_stride || (d_b && !b_stride)) return fail(CG_ERR_ARG, "cg_vec_mismatch_dev: a stride must be at least 1");
+    HIPCHK(hipSetDevice(ctx->device));
+    return with_fr(curve, [&](auto tag) -> int {
+        typedef decltype(tag) Fr;
+        StatScope ss(ctx, TAG_VEC);
+        return launch_vec_mismatch<Fr>(ctx->stream, (const Fr*)d_a, a_stride, (const Fr*)d_b, b_stride, first, n, (unsigned long long*)d_result);
+    });
+}
 int32_t cg_spmv_csr_dev(cg_ctx* ctx, int32_t curve, const uint32_t* d_row_ptr, const uint32_t* d_col, const void* d_coeff, size_t n_rows,
                         const void* d_pub, uint32_t n_inputs, int32_t party, const void* d_wit_a, const void* d_wit_b, void* d_out_a, void* d_out_b) {
     if (!ctx || !d_row_ptr || !d_out_a || !d_wit_a) return fail(CG_ERR_ARG, "null argument");

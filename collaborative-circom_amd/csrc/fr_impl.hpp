@@ -96,6 +96,23 @@ CG_PLONK_LAUNCH(launch_plonk_mul4_tail, k_plonk_mul4_tail, PlonkMul4Args)
 CG_PLONK_LAUNCH(launch_plonk_r3_t, k_plonk_r3_t, PlonkTArgs)
 CG_PLONK_LAUNCH(launch_plonk_r3_divide, k_plonk_r3_divide, PlonkDivArgs)
 #undef CG_PLONK_LAUNCH
+template <class Fr> int launch_plonk_gate_check(hipStream_t st, const PlonkCheckArgs<Fr>& g, size_t n, unsigned long long* result) {
+    static const unsigned long long init[2] = {0ull, ~0ull};
+    HIPCHK(hipMemcpyAsync(result, init, sizeof init, hipMemcpyHostToDevice, st));
+    if (!n) return 0;
+    hipLaunchKernelGGL((k_plonk_gate_check<Fr>), dim3(grid_for(n)), dim3(256), 0, st, g, n, result);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+template <class Fr> int launch_vec_mismatch(hipStream_t st, const Fr* a, size_t a_stride, const Fr* b, size_t b_stride, size_t first, size_t n, unsigned long long* result) {
+    static const unsigned long long init[2] = {0ull, ~0ull};
+    HIPCHK(hipMemcpyAsync(result, init, sizeof init, hipMemcpyHostToDevice, st));
+    if (first >= n) return 0;
+    if (b) hipLaunchKernelGGL((k_vec_mismatch<Fr, false>), dim3(grid_for(n - first)), dim3(256), 0, st, a, a_stride, b, b_stride, first, n, result);
+    else hipLaunchKernelGGL((k_vec_mismatch<Fr, true>), dim3(grid_for(n - first)), dim3(256), 0, st, a, a_stride, b, b_stride, first, n, result);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
 // scratch: ceil(n / 2048) elements; op 0 = product, 1 = sum
 template <class Fr, int OP> int launch_prefix_op(hipStream_t st, Fr* out, const Fr* in, size_t n, Fr* scratch) {
     const size_t tile = (size_t)256 * SCAN_ITEMS, ntiles = (n + tile - 1) / tile;
@@ -370,6 +387,8 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
     template decltype(launch_plonk_mul4_tail<Fr>) launch_plonk_mul4_tail<Fr>;                                              \
     template decltype(launch_plonk_r3_t<Fr>) launch_plonk_r3_t<Fr>;                                                        \
     template decltype(launch_plonk_r3_divide<Fr>) launch_plonk_r3_divide<Fr>;                                              \
+    template decltype(launch_plonk_gate_check<Fr>) launch_plonk_gate_check<Fr>;                                            \
+    template decltype(launch_vec_mismatch<Fr>) launch_vec_mismatch<Fr>;                                                    \
     template decltype(launch_spmv_csr<Fr>) launch_spmv_csr<Fr>;                                                            \
     template decltype(launch_r1cs_check<Fr>) launch_r1cs_check<Fr>;                                                        \
     template decltype(launch_qap_columns<Fr>) launch_qap_columns<Fr>;                                                      \

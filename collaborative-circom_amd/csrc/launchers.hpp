@@ -19,6 +19,7 @@ template <class F> struct PlonkGateArgs;
 template <class F> struct PlonkMul4Args;
 template <class F> struct PlonkTArgs;
 template <class F> struct PlonkDivArgs;
+template <class F> struct PlonkCheckArgs;
 
 // ---- scalar side of the MSM (msm_sort_kernels.hpp, fr_impl.hpp): digits, histogram, scan, scatter
 constexpr int SCAN_TILE = 2048;         // k_scan_*: counters per workgroup (256 lanes x 8)
@@ -107,6 +108,9 @@ template <class Fr> int launch_plonk_r3_gate(hipStream_t st, const PlonkGateArgs
 template <class Fr> int launch_plonk_mul4_tail(hipStream_t st, const PlonkMul4Args<Fr>& g, size_t n);
 template <class Fr> int launch_plonk_r3_t(hipStream_t st, const PlonkTArgs<Fr>& g, size_t n);
 template <class Fr> int launch_plonk_r3_divide(hipStream_t st, const PlonkDivArgs<Fr>& g, size_t n);
+// result (both): count, smallest failing row / differing position (set by the launcher first).  vec_mismatch: b == nullptr compares a with zero.
+template <class Fr> int launch_plonk_gate_check(hipStream_t st, const PlonkCheckArgs<Fr>& g, size_t n, unsigned long long* result);
+template <class Fr> int launch_vec_mismatch(hipStream_t st, const Fr* a, size_t a_stride, const Fr* b, size_t b_stride, size_t first, size_t n, unsigned long long* result);
 template <class Fr> int launch_build_twiddles_lazy(hipStream_t st, void* tw, size_t m, int log_m, const Fr* lo, const Fr* hi, int log_lo, const Fr& c32);
 template <class Fr> int launch_build_twiddles_lazy_natural(hipStream_t st, void* tw, size_t m, const Fr* lo, const Fr* hi, int log_lo, const Fr& c32);
 template <class Fr> int launch_ntt_ct_pass(hipStream_t st, bool first, NttVecs src, NttVecs dst, int nvec, size_t n, int log_m, int s0, int k, int t, const void* tw);

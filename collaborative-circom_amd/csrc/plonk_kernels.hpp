@@ -4,6 +4,7 @@
 // of CoPlonk did with add_with_public.  Field arithmetic is exact, so summing in another order gives the same bits.
 #pragma once
 #include "vec_kernels.hpp"
+#include "r1cs_kernels.hpp"
 
 namespace cg {
 
@@ -162,6 +163,55 @@ __global__ void __launch_bounds__(256) k_plonk_r3_divide(PlonkDivArgs<F> g, size
             }
         }
     }
+}
+
+// ---- a witness against the gates of a key, and exact comparisons of resident vectors ---------------------------------------------------
+// The value of wire `id` as round 1 and k_plonk_additions read it: pub[id] for id < n_inputs (= n_public + 1; the caller keeps pub[0] = 0,
+// types.rs:107-109), else the extended witness (private part, then the additions).
+template <class F>
+__device__ __forceinline__ F plonk_wire(uint32_t id, const F* __restrict__ pub, uint32_t n_inputs, const F* __restrict__ ext) {
+    return id < n_inputs ? ld_fp(pub + id) : ld_fp(ext + (id - n_inputs));
+}
+// A lane per row i < n of the domain: res = qm a b + ql a + qr b + qo c + qc - (i < n_public ? w[i + 1] : 0) with a, b, c the wires
+// map[0..2][i] for i < n_constraints and zero on the padding rows (which are checked too: a key with a selector there fails them for every
+// witness).  q[s][i * q_stride]: the 4n evaluations of a session with a stride of 4, or a vector of its own.  A row that names a wire
+// >= n_wires is counted as failing and nothing is read for it.  Ends as k_r1cs_check (r1cs_report).  blockDim.x == 256.
+template <class F> struct PlonkCheckArgs { const uint32_t* map[3]; const F* q[5]; size_t q_stride; size_t n_constraints; const F* pub; uint32_t n_public; const F* ext; uint32_t n_wires; };
+template <class F>
+__global__ void __launch_bounds__(256) k_plonk_gate_check(PlonkCheckArgs<F> g, size_t n, unsigned long long* __restrict__ result) {
+    unsigned long long count = 0, first = ~0ull;
+    const uint32_t n_inputs = g.n_public + 1;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t o = i * g.q_stride;
+        F res = ld_fp(g.q[4] + o);
+        bool bad = false;
+        if (i < g.n_constraints) {
+            const uint32_t ia = g.map[0][i], ib = g.map[1][i], ic = g.map[2][i];
+            bad = ia >= g.n_wires || ib >= g.n_wires || ic >= g.n_wires;
+            if (!bad) {
+                const F a = plonk_wire<F>(ia, g.pub, n_inputs, g.ext), b = plonk_wire<F>(ib, g.pub, n_inputs, g.ext);
+                res = res + (ld_fp(g.q[0] + o) * b + ld_fp(g.q[1] + o)) * a + ld_fp(g.q[2] + o) * b + ld_fp(g.q[3] + o) * plonk_wire<F>(ic, g.pub, n_inputs, g.ext);
+            }
+        }
+        if (i < g.n_public) res = res - ld_fp(g.pub + i + 1);
+        if (bad || !res.is_zero()) { count++; first = i < first ? i : first; }         // rows ascend per lane: the first hit is the smallest
+    }
+    r1cs_report(count, first, result);
+}
+// The positions first <= i < n at which a[i * a_stride] != b[i * b_stride], or (ZERO) at which a[i * a_stride] != 0: count and smallest i.
+// The elements are compared as stored (limb by limb).  Ends as k_r1cs_check.  blockDim.x == 256.
+template <class F, bool ZERO>
+__global__ void __launch_bounds__(256) k_vec_mismatch(const F* __restrict__ a, size_t a_stride, const F* __restrict__ b, size_t b_stride, size_t first_row, size_t n,
+                                                      unsigned long long* __restrict__ result) {
+    unsigned long long count = 0, first = ~0ull;
+    for (size_t i = first_row + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const F x = ld_fp(a + i * a_stride);
+        bool differ;
+        if (ZERO) differ = !x.is_zero();
+        else { const F y = ld_fp(b + i * b_stride); differ = x != y; }
+        if (differ) { count++; first = i < first ? i : first; }
+    }
+    r1cs_report(count, first, result);
 }
 
 }  // namespace cg

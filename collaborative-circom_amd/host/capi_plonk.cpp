@@ -1,6 +1,7 @@
 // C entry points: co-plonk (co-plonk/src/plonk.rs:133-271 drives round1..round5)
 #include "plonk.hpp"
 #include "plonk_verify.hpp"
+#include "plonk_audit.hpp"
 #include "capi_common.hpp"
 
 #include <chrono>
@@ -317,7 +318,8 @@ struct cgh_plonk_session {
     std::unique_ptr<cgh::PlonkResident> res;
     std::unique_ptr<cgh::PlonkVerifyingKey> vk;                                          // cgh_plonk_session_verify: prepared from the zkey's header at first use (under vk_mu)
     std::mutex mu, vk_mu;
-    ~cgh_plonk_session() { res.reset(); if (ctx) cg_ctx_destroy(ctx); }
+    void* q_rows[5] = {};                                                                // cgh_plonk_session_check_witness: the selectors on the n rows, gathered at first use (under mu)
+    ~cgh_plonk_session() { for (void* p : q_rows) if (p) cg_dev_free(ctx, p); res.reset(); if (ctx) cg_ctx_destroy(ctx); }
 };
 namespace {
 cgh_plonk_session* plonk_session(void* s, const char* who) { if (!s) throw std::runtime_error(std::string(who) + ": null session"); return (cgh_plonk_session*)s; }
@@ -372,6 +374,36 @@ int32_t cgh_plonk_session_prove_plain(void* session, const uint64_t* full_witnes
         if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         return 0;
     } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
+}
+int32_t cgh_plonk_session_check_witness(void* session, const uint64_t* full_witness, uint64_t* n_bad, uint64_t* first_bad) {
+    cgh_plonk_session* s = nullptr;
+    try {
+        s = plonk_session(session, "cgh_plonk_session_check_witness");
+        if (!full_witness || !n_bad || !first_bad) throw std::runtime_error("cgh_plonk_session_check_witness: null argument");
+        std::lock_guard<std::mutex> lock(s->mu);
+        const size_t n = s->res->z.domain_size;
+        for (int i = 0; i < 5; i++) if (!s->q_rows[i]) {                               // 5 n elements, kept until close
+            void* p = nullptr;
+            if (cg_dev_alloc(s->ctx, n * 32, &p)) cgh::die("cg_dev_alloc");
+            if (cg_vec_gather_strided_dev(s->ctx, s->res->z.curve.id, p, s->res->q_eval[i], n, 0, 4)) { cg_dev_free(s->ctx, p); cgh::die("cg_vec_gather_strided_dev"); }
+            s->q_rows[i] = p;
+        }
+        cgh::plonk_check_witness(s->ctx, *s->res, s->q_rows, (const cgh::Fr*)full_witness, n_bad, first_bad);
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
+}
+int32_t cgh_plonk_session_audit_timed(void* session, void* r1cs, const uint8_t* seed32, uint32_t* failed, uint64_t* detail, double* stage_seconds) {
+    cgh_plonk_session* s = nullptr;
+    try {
+        s = plonk_session(session, "cgh_plonk_session_audit");
+        if (!failed || !detail) throw std::runtime_error("cgh_plonk_session_audit: null argument");
+        std::lock_guard<std::mutex> lock(s->mu);
+        cgh::plonk_audit(s->ctx, *s->res, (cgh::R1csHandle*)r1cs, seed32, failed, detail, stage_seconds);
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); plonk_session_settle(s); return 1; }
+}
+int32_t cgh_plonk_session_audit(void* session, void* r1cs, const uint8_t* seed32, uint32_t* failed, uint64_t* detail) {
+    return cgh_plonk_session_audit_timed(session, r1cs, seed32, failed, detail, nullptr);
 }
 int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in, const uint64_t* wit_a, const uint64_t* wit_b, const uint64_t* blind_a, const uint64_t* blind_b,
                                            const cgh_rep3_net* net, const cgh_rep3_rand* rnd, const cgh_rep3_chacha* streams, uint64_t* commits, uint64_t* evals,

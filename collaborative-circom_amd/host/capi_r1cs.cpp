@@ -1,5 +1,6 @@
 // C entry points: .r1cs handles, the witness check, the Groth16 and Plonk development setups (include/cogroth16_host.h)
 #include "plonk_setup.hpp"
+#include "plonk_audit.hpp"
 #include "capi_common.hpp"
 
 extern "C" {
@@ -66,6 +67,13 @@ int32_t cgh_r1cs_plonk_info(int32_t device, void* r1cs, size_t* out4) {
         if (!r1cs || !out4) throw std::runtime_error("cgh_r1cs_plonk_info: null argument");
         const cgh::PlonkPlan p = cgh::r1cs_plonk_info(*(cgh::R1csHandle*)r1cs, device);
         out4[0] = p.n_additions; out4[1] = p.n_constraints; out4[2] = p.n_vars; out4[3] = p.n;
+        return 0;
+    } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
+}
+int32_t cgh_r1cs_plonk_gate_origin(int32_t device, void* r1cs, uint64_t gate_row, uint64_t* out3) {
+    try {
+        if (!r1cs || !out3) throw std::runtime_error("cgh_r1cs_plonk_gate_origin: null argument");
+        cgh::r1cs_plonk_gate_origin(*(cgh::R1csHandle*)r1cs, device, gate_row, out3);
         return 0;
     } catch (const std::exception& e) { g_host_err = e.what(); return 1; }
 }

@@ -21,6 +21,8 @@ struct PlonkZKey {   // circom-types/src/plonk/zkey.rs:18-42 (the fields round 1
     std::vector<Fr> q_eval[5];       // qm, ql, qr, qo, qc on the extended domain (sections 7..11)
     std::vector<std::vector<Fr>> lagrange_eval;   // n_public polynomials on the extended domain (section 13)
     std::vector<Fr> q_coef[5], sigma_coef[3];     // coefficient forms (rounds 4 and 5)
+    std::vector<std::vector<Fr>> lagrange_coef;   // the coefficient forms of section 13 (the key audit, plonk_audit.hpp)
+    std::map<uint32_t, size_t> section_bytes;     // the length of every section as the file states it (the key audit)
 };
 static PlonkZKey read_plonk_zkey(int curve_id, const std::string& path) {   // zkey.rs:83-255, header :373-424
     Curve c{curve_id};
@@ -35,6 +37,7 @@ static PlonkZKey read_plonk_zkey(int curve_id, const std::string& path) {   // z
     auto section = [&](uint32_t id) { auto it = sec.find(id); if (it == sec.end()) throw std::runtime_error("missing zkey section"); return Cursor{buf.data() + it->second.first, it->second.second}; };
     if (section(1).u32() != 2) throw std::runtime_error("not a plonk zkey");
     PlonkZKey z; z.curve = c;
+    for (const auto& kv : sec) z.section_bytes[kv.first] = kv.second.second;
     Cursor h = section(2);
     if (h.u32() != c.fq()) throw std::runtime_error("unexpected base field byte size");
     uint64_t q[6] = {0}; h.bytes(q, c.fq());
@@ -57,7 +60,7 @@ static PlonkZKey read_plonk_zkey(int curve_id, const std::string& path) {   // z
         }
     }
     for (int k = 0; k < 5; k++) { Cursor q = section(7 + k); z.q_coef[k].resize(z.domain_size); q.bytes(z.q_coef[k].data(), z.domain_size * 32); z.q_eval[k].resize(4 * z.domain_size); q.bytes(z.q_eval[k].data(), 4 * z.domain_size * 32); }
-    { Cursor l = section(13); z.lagrange_eval.resize(z.n_public); for (auto& v : z.lagrange_eval) { l.need(z.domain_size * 32); l.off += z.domain_size * 32; v.resize(4 * z.domain_size); l.bytes(v.data(), 4 * z.domain_size * 32); } }
+    { Cursor l = section(13); z.lagrange_eval.resize(z.n_public); z.lagrange_coef.resize(z.n_public); for (size_t j = 0; j < z.n_public; j++) { auto& v = z.lagrange_eval[j]; z.lagrange_coef[j].resize(z.domain_size); l.bytes(z.lagrange_coef[j].data(), z.domain_size * 32); v.resize(4 * z.domain_size); l.bytes(v.data(), 4 * z.domain_size * 32); } }
     { Cursor a = section(3); z.additions.resize(z.n_additions); for (auto& e : z.additions) { e.id1 = a.u32(); e.id2 = a.u32(); a.bytes(e.f1.v, 32); a.bytes(e.f2.v, 32); } }
     for (int k = 0; k < 3; k++) { Cursor m = section(4 + k); z.map[k].resize(z.n_constraints); for (auto& v : z.map[k]) v = m.u32(); }
     { Cursor t = section(14); z.p_tau.resize((z.domain_size + 6) * c.aff(CG_G1)); t.bytes(z.p_tau.data(), z.p_tau.size()); }
@@ -74,6 +77,7 @@ struct PlonkResident {
     cg_bases* tau = nullptr;
     void* q_eval[5] = {}; void* q_coef[5] = {}; void* sigma_eval[3] = {}; void* sigma_coef[3] = {};
     void* lagrange = nullptr;                 // n_public vectors of 4n evaluations, back to back
+    void* lagrange_coef = nullptr;            // their n coefficients each, back to back (read by the key audit only)
     void* pw = nullptr;                       // omega4^i, i < 4n
     uint32_t* row_ptr = nullptr; uint32_t* col[3] = {}; void* ones = nullptr;   // round 1: wire w, row i = signal map[w][i] with coefficient one
     // additions (round1.rs:209-238): addition a writes extended-witness entry n_priv + a; level l = order[level_off[l] .. level_off[l + 1])
@@ -114,6 +118,8 @@ private:
         for (int i = 0; i < 3; i++) { sigma_eval[i] = put(z.sigma_eval[i]); sigma_coef[i] = put(z.sigma_coef[i]); std::vector<Fr>().swap(z.sigma_eval[i]); std::vector<Fr>().swap(z.sigma_coef[i]); }
         lagrange = dev(z.n_public * N * 32);
         for (size_t j = 0; j < z.n_public; j++) { CG(cg_dev_upload(ctx, (uint8_t*)lagrange + j * N * 32, z.lagrange_eval[j].data(), N * 32)); std::vector<Fr>().swap(z.lagrange_eval[j]); }
+        lagrange_coef = dev(z.n_public * n * 32);
+        for (size_t j = 0; j < z.n_public; j++) { CG(cg_dev_upload(ctx, (uint8_t*)lagrange_coef + j * n * 32, z.lagrange_coef[j].data(), n * 32)); std::vector<Fr>().swap(z.lagrange_coef[j]); }
         const Fr one = fr_from_u64(c, 1);
         pw = dev(N * 32); CG(cg_vec_fill_dev(ctx, c.id, pw, N, one.v)); CG(cg_vec_distribute_powers_dev(ctx, c.id, pw, N, snarkjs_roots(c).roots[z.power + 2].v, one.v));
         std::vector<uint32_t> rp(nc + 1); for (size_t i = 0; i <= nc; i++) rp[i] = (uint32_t)i;

@@ -408,6 +408,21 @@ int32_t cg_plonk_mul4_tail_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, 
 int32_t cg_plonk_r3_t_dev(cg_ctx* ctx, int32_t curve, int32_t k, int32_t public_component, size_t n, const void* d_l1, const void* const* d_in,
                           const void* h_alpha, void* const* d_out);
 int32_t cg_plonk_r3_divide_dev(cg_ctx* ctx, int32_t curve, int32_t k, size_t n, void* const* d_t, const void* const* d_tz);
+/* A PLAIN witness against the gates of a Plonk key in one pass, a lane per row: d_result[0] = the number of rows i < domain_size with
+ *   qm[i] a b + ql[i] a + qr[i] b + qo[i] c + qc[i] - (i < n_public ? w[i + 1] : 0) != 0,
+ * d_result[1] = the smallest such row, 2^64 - 1 when there is none (two u64; the call initialises them).  a, b, c = w[d_maps[0..2][i]] for
+ * i < n_constraints and zero on the padding rows, which are checked too (a nonzero selector there fails for every witness).  w[id] is read
+ * as round 1 and cg_plonk_additions_dev read it: d_pub[id] for id <= n_public (n_public + 1 elements; the caller keeps d_pub[0] = 0, as the
+ * prover forces it), else d_ext[id - n_public - 1] (the private witness, then the additions).  A row that names a wire >= n_wires counts as
+ * failing and reads nothing.  d_q = qm, ql, qr, qo, qc, element i at d_q[s][i * q_stride]: a stride of 4 reads the 4n evaluations of a zkey
+ * where they lie.  Secret-shared witnesses are out of scope, as for cg_r1cs_check_dev.  Failures are counted per wave, one atomic pair per
+ * workgroup. */
+int32_t cg_plonk_gate_check_dev(cg_ctx* ctx, int32_t curve, const uint32_t* const* d_maps, size_t n_constraints, const void* const* d_q, size_t q_stride, size_t domain_size,
+                                const void* d_pub, uint32_t n_public, const void* d_ext, size_t n_wires, void* d_result);
+/* Exact comparison of two resident vectors: d_result[0] = the number of positions first <= i < n with d_a[i * a_stride] != d_b[i * b_stride]
+ * (elements compared as stored), d_result[1] = the smallest such i, 2^64 - 1 when there is none (two u64; the call initialises them).
+ * d_b NULL: d_a is compared with zero over the same range. */
+int32_t cg_vec_mismatch_dev(cg_ctx* ctx, int32_t curve, const void* d_a, size_t a_stride, const void* d_b, size_t b_stride, size_t first, size_t n, void* d_result);
 /* host-buffer forms of the two elementwise products (what an unmodified `&mut Vec<F>` caller would use) */
 int32_t cg_vec_mul(cg_ctx* ctx, int32_t curve, void* h_out, const void* h_a, const void* h_b, size_t n);
 int32_t cg_vec_rep3_mul_local(cg_ctx* ctx, int32_t curve, void* h_out, const void* h_aa, const void* h_ab,

@@ -334,6 +334,52 @@ int32_t cgh_plonk_session_prove_rep3_party(void* session, const uint64_t* pub_in
                                            const uint64_t* blind_a, const uint64_t* blind_b, const cgh_rep3_net* net,
                                            const cgh_rep3_rand* rnd, const cgh_rep3_chacha* streams,
                                            uint64_t* commits, uint64_t* evals, uint64_t* challenges, double* seconds);
+/* Which gate does a witness break?  full_witness as for cgh_plonk_session_prove_plain (n_vars - n_additions Montgomery elements: the
+ * leading one, the public inputs, the private witness).  The witness is uploaded, the session's resident addition schedule extends it, and
+ * one pass of cg_plonk_gate_check_dev reads the resident wire maps and the five selectors on the n rows (contiguous copies of every fourth
+ * resident evaluation, gathered at the first call and kept until close: 5 n elements, 160 MiB at 2^20 - measurably faster than reading the
+ * 4n evaluations with a stride of 4, profiles/plonk_audit_timing.txt):
+ * *n_bad = the number of rows i < domain_size with qm a b + ql a + qr b + qo c + qc - PI_i != 0 (the padding rows included, where a, b, c
+ * are zero), *first_bad = the smallest such row, 2^64 - 1 when there is none.  No transform, no MSM, no randomness.  Secret-shared
+ * witnesses are OUT OF SCOPE, for the reason cgh_r1cs_check_witness gives: the gate multiplies two witness values, which no party can do
+ * on shares alone.  cgh_r1cs_plonk_gate_origin turns first_bad into a row of the circuit. */
+int32_t cgh_plonk_session_check_witness(void* session, const uint64_t* full_witness, uint64_t* n_bad, uint64_t* first_bad);
+/* Is this key the key `plonk setup` writes?  A Plonk key is a deterministic function of its circuit and of the SRS inside it, so all of it
+ * can be audited without a secret.  *failed = one bit per check that found something, detail[2 k], detail[2 k + 1] for check k (bit 1 << k)
+ * = which polynomial, section or part, and the first offending index (both 2^64 - 1 for a check that passed; CGH_PLONK_AUDIT_CHECKS pairs).
+ * Polynomials are numbered 0 .. 4 = Qm, Ql, Qr, Qo, Qc, 5 .. 7 = S1, S2, S3, 8 + j = Lagrange polynomial j.  Every check runs whatever the
+ * others found.  All but BLOCKS read the COEFFICIENT forms, brought to the n rows by one forward n-point transform each; BLOCKS alone
+ * ties the 4n evaluations to the coefficients, so that one defect sets predictable bits.
+ *   HEADER       k1, k2 are what `plonk setup` finds for the domain (detail: 2, 0 / 1) and every section has the length the header numbers
+ *                give (detail: the section, its length).  A key whose sizes are meaningless - more gates than rows, a map entry that is no
+ *                variable - is an ERROR status with a cgh_last_error text, as is (at cgh_plonk_session_open already) an addition that reads
+ *                anything but an input or an earlier addition.
+ *   BLOCKS       for each of the 8 + n_public polynomials the stored 4n evaluations are the 4n-point transform of the stored coefficients
+ *                (cg_ntt_dev in batches of 8, cg_vec_mismatch_dev); detail: the polynomial, the evaluation.
+ *   ROWS         every selector is zero on the rows >= n_constraints; Lagrange polynomial j is 1 on row j, 0 elsewhere; detail: polynomial, row.
+ *   SIGMA        S1, S2, S3 on the n rows are the labels cg_plonk_sigma_labels_dev gives for the key's own maps: the previous position of the
+ *                same wire, rows then columns, wire 0 on the padding rows.  The STRICT test: the permutation snarkjs writes, not any
+ *                permutation with the same cycles.  detail: polynomial, row.
+ *   COMMITMENTS  each of the header's Qm .. S3 is cg_msm_dev of its coefficients over the first n points of p_tau; detail: polynomial, -.
+ *   SRS          p_tau[0] is the generator (detail 0, 0) and, with rho_0 = 1 and 128-bit rho_i from ChaCha12 (seed32, or OS entropy when
+ *                NULL; drawn as cgh_plonk_verify_batch draws its coefficients), e(sum rho_i P_(i+1), G_2) e(-sum rho_i P_i, X_2) = 1 over
+ *                i < n + 5 (detail 1, -): two MSMs over the session's table at offsets 1 and 0, then cg_pairing_check.  An SRS that is not
+ *                the powers of one tau with X_2 = tau G_2 passes with probability at most 2^-128.
+ *   CIRCUIT      only with an .r1cs handle (NULL: skipped): the header numbers (detail 2, 0 .. 4 = nVars, nPublic, domain, nAdditions,
+ *                nConstraints), sections 3 - 6 (detail: section, addition or row) and the five selectors on the n rows (detail: section
+ *                7 .. 11, row) equal a fresh cg_plonk_gates_count_dev + cg_plonk_gates_emit_dev for the circuit.  A curve or size mismatch
+ *                sets the bit (detail 2, -), it is no error.
+ * _timed: stage_seconds[7] (optional) = header, transforms, comparisons, the eight MSMs, the two SRS MSMs, pairing, circuit. */
+#define CGH_PLONK_AUDIT_HEADER 1u
+#define CGH_PLONK_AUDIT_BLOCKS 2u
+#define CGH_PLONK_AUDIT_ROWS 4u
+#define CGH_PLONK_AUDIT_SIGMA 8u
+#define CGH_PLONK_AUDIT_COMMITMENTS 16u
+#define CGH_PLONK_AUDIT_SRS 32u
+#define CGH_PLONK_AUDIT_CIRCUIT 64u
+#define CGH_PLONK_AUDIT_CHECKS 7
+int32_t cgh_plonk_session_audit(void* session, void* r1cs, const uint8_t* seed32, uint32_t* failed, uint64_t* detail);
+int32_t cgh_plonk_session_audit_timed(void* session, void* r1cs, const uint8_t* seed32, uint32_t* failed, uint64_t* detail, double* stage_seconds);
 /* The Shamir party on a session (rounds 1..5; arguments as cgh_plonk_prove_shamir_party), and the same party with its private randomness
  * as ONE 32-byte seed: the library's own ChaCha12 stream, the large draws (preprocessing, the king's re-sharing coefficients) made on the GPU
  * by cg_chacha12_fr_rand_dev, as cgh_session_prove_shamir_party_seeded does.  A failing callback ends the call with a status and a
@@ -404,6 +450,15 @@ int32_t cgh_setup_toxic(int32_t curve, uint64_t seed, uint64_t* out5);
  * transforms of the Lagrange polynomials; file writes (scripts/plonk_setup_timing.py).
  * The canonical matrices are uploaded at the first call per device and stay there until the handle closes. */
 int32_t cgh_r1cs_plonk_info(int32_t device, void* r1cs, size_t* out4);
+/* Where a gate row of the circuit's Plonk key comes from (what turns the first_bad of cgh_plonk_session_check_witness into something a
+ * circuit author can read): out3 = kind, the R1CS row, the index of the addition within that row's additions; 2^64 - 1 where a field does
+ * not apply (public-input and padding rows have no R1CS row, only an addition has an index).  Read off the count pass's offsets on the
+ * host.  A row outside the domain is an error status. */
+#define CGH_PLONK_GATE_PUBLIC 0
+#define CGH_PLONK_GATE_ADDITION 1
+#define CGH_PLONK_GATE_CONSTRAINT 2
+#define CGH_PLONK_GATE_PADDING 3
+int32_t cgh_r1cs_plonk_gate_origin(int32_t device, void* r1cs, uint64_t gate_row, uint64_t* out3);
 int32_t cgh_setup_plonk_dev(int32_t device, void* r1cs, uint64_t seed, const char* zkey_path);
 int32_t cgh_setup_plonk_tau_dev(int32_t device, void* r1cs, const uint64_t* tau, const char* zkey_path, double* stage_seconds);
 
