@@ -5,6 +5,7 @@ This module is only a thin ctypes loader over it (directory name contains a hyph
 `importlib.import_module("collaborative-circom_amd")`).  There is NO CPU fallback: `load()` raises if the library is
 missing, and `Context()` raises if no HIP device is present.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -48,13 +49,18 @@ GOPT_SUBGROUP_FULL, GOPT_COMPACT_MIN_LOG, GOPT_SORT_STAGING, GOPT_SORT_SMALL, GO
 # paths of the MSM's scalar-side schedule (cg_msm_schedule_dev: 1 .. 4 can be forced, all five are reported) and the scalar fields' bit lengths
 MSM_PATH_GENERAL, MSM_PATH_SMALL, MSM_PATH_PARTITION, MSM_PATH_DIRECT, MSM_PATH_PARTITION_UNSTAGED = 1, 2, 3, 4, 5
 FR_BITS = {0: 254, 1: 255}
+# cg_msm_stages_dev: reduction kinds, the geometry record (include/cogroth16_hip.h) and what it returns
+MSM_REDUCE_SEGMENTS, MSM_REDUCE_BITSUM, MSM_REDUCE_GRID, MSM_GEOM_WORDS = 0, 1, 2, 16
+MSM_MAX_PARTIALS = 512                   # classic: one per window (at most 128); bit sums: c; grid: 264 at c = 22
+MsmStageGeom = collections.namedtuple("MsmStageGeom", "kind ngroups nchunks nb nsets seg_len segs group_segs bit_groups log_l log_h gc gr chunk_len slice_groups nwin")
+MsmStages = collections.namedtuple("MsmStages", "geom acc_buckets acc_cont cont_state cont_bucket merged_buckets partials folded")
 
 # every symbol include/cogroth16_hip.h declares (checked by tests/test_abi_surface.py)
 ABI_SYMBOLS = [
     "cg_ctx_create", "cg_ctx_create_ex", "cg_ctx_destroy", "cg_ctx_sync", "cg_ctx_stream", "cg_ctx_set_stream", "cg_last_error", "cg_version",
     "cg_dev_alloc", "cg_dev_free", "cg_dev_free_many", "cg_dev_cache_trim", "cg_stream_group_begin", "cg_stream_group_end", "cg_dev_upload", "cg_dev_download", "cg_dev_memset_zero",
     "cg_bases_register", "cg_bases_register_device", "cg_bases_release", "cg_bases_len", "cg_bases_precompute", "cg_bases_check_on_curve", "cg_bases_check_subgroup",
-    "cg_msm", "cg_msm_dev", "cg_msm_dev_begin", "cg_msm_dev_begin_multi", "cg_msm_end", "cg_msm_set_window", "cg_msm_set_chunk", "cg_ctx_set_option", "cg_ctx_get_option", "cg_set_option", "cg_get_option", "cg_msm_scalars_after", "cg_msm_set_scatter_capacity", "cg_msm_schedule_dev",
+    "cg_msm", "cg_msm_dev", "cg_msm_dev_begin", "cg_msm_dev_begin_multi", "cg_msm_end", "cg_msm_set_window", "cg_msm_set_chunk", "cg_ctx_set_option", "cg_ctx_get_option", "cg_set_option", "cg_get_option", "cg_msm_scalars_after", "cg_msm_set_scatter_capacity", "cg_msm_schedule_dev", "cg_msm_stages_dev",
     "cg_ntt", "cg_ntt_dev", "cg_ntt_coset_pair_dev", "cg_chacha12_fr_rand_dev", "cg_chacha12_fr_rand_dev_begin", "cg_chacha12_fr_rand_dev_finish",
     "cg_host_alloc", "cg_host_free", "cg_host_is_pinned", "cg_dev_download_begin", "cg_dev_upload_begin", "cg_stream_mark", "cg_dev_download_begin_after", "cg_copy_wait", "cg_copy_fence",
     "cg_vec_add_dev", "cg_vec_sub_dev", "cg_vec_mul_dev", "cg_vec_rep3_mul_local_dev", "cg_vec_distribute_powers_dev", "cg_vec_affine_dev", "cg_vec_fill_dev", "cg_vec_gather_strided_dev", "cg_vec_lincomb_dev", "cg_shamir_share_dev", "cg_vec_prefix_prod_dev", "cg_vec_prefix_sum_dev", "cg_vec_inverse_dev",
@@ -460,6 +466,37 @@ class Context:
         _chk(load().cg_msm_schedule_dev(self.h, int(curve), _dp(d_scalars), C.c_size_t(n), int(c), int(bool(shared)), int(path), C.c_uint32(cap), _hp(counts), _hp(offsets), _hp(sorted_),
                                         C.byref(taken), C.byref(overflow)))
         return counts, offsets, sorted_, taken.value, overflow.value
+
+    def msm_stages(self, bases, c, entries, chunk_len, schedules, cap=0, want=("acc", "merged", "partials", "folded"), out=None):
+        """the point side of the MSM stage by stage (cg_msm_stages_dev) over `schedules` = [(counts, offsets, sorted)] of uint32 host arrays, one
+        per set -> MsmStages.  want: which stages come down ("acc" = buckets, continuation pieces with states and tags after the accumulation;
+        "merged" = buckets after the merges; "partials"; "folded").  out: a dict of arrays to fill instead of new ones (tests of refusals)."""
+        nsets = len(schedules)
+        nwin = FR_BITS[bases.curve] // int(c) + 1
+        scheds = [tuple(np.ascontiguousarray(a, dtype=np.uint32) for a in s) for s in schedules]
+        nbuckets = scheds[0][0].size
+        nchunks = max(1, -(-int(entries) // max(int(chunk_len), 1)))
+        aw, jw = point_words(bases.curve, bases.group, 2), point_words(bases.curve, bases.group, 3)
+        geom = np.zeros(MSM_GEOM_WORDS, dtype=np.uint32)
+        o = dict(out or {})
+        if "acc" in want:
+            o.setdefault("acc_buckets", np.empty((nsets, nbuckets, aw), dtype=np.uint64)); o.setdefault("acc_cont", np.empty((nsets, nchunks, aw), dtype=np.uint64))
+            o.setdefault("cont_state", np.empty((nsets, nchunks), dtype=np.uint32)); o.setdefault("cont_bucket", np.empty((nsets, nchunks), dtype=np.uint32))
+        if "merged" in want:
+            o.setdefault("merged_buckets", np.empty((nsets, nbuckets, aw), dtype=np.uint64))
+        if "partials" in want:                             # how many there are per set comes back in the geometry record: room for the most any window gives
+            o.setdefault("partials", np.empty(nsets * MSM_MAX_PARTIALS * jw, dtype=np.uint64))
+        if "folded" in want:
+            o.setdefault("folded", np.empty((nsets, jw), dtype=np.uint64))
+        ptrs = [(C.c_void_p * nsets)(*[s[k].ctypes.data for s in scheds]) for k in range(3)]
+        _chk(load().cg_msm_stages_dev(self.h, bases.h, int(c), C.c_size_t(int(entries)), C.c_uint32(int(chunk_len)), C.c_uint32(int(cap)), nsets, ptrs[0], ptrs[1], ptrs[2],
+                                      _hp(o.get("acc_buckets")), _hp(o.get("acc_cont")), _hp(o.get("cont_state")), _hp(o.get("cont_bucket")), _hp(o.get("merged_buckets")),
+                                      _hp(o.get("partials")), _hp(o.get("folded")), _hp(geom)))
+        g = MsmStageGeom(*[int(v) for v in geom])
+        assert g.nchunks == nchunks and g.nwin == nwin and g.ngroups <= MSM_MAX_PARTIALS, g
+        if o.get("partials") is not None and o["partials"].ndim == 1:
+            o["partials"] = o["partials"][:nsets * g.ngroups * jw].reshape(nsets, g.ngroups, jw)
+        return MsmStages(geom=g, **{k: o.get(k) for k in MsmStages._fields if k != "geom"})
 
     # ---- NTT
     def ntt(self, curve, vecs, group_gen, inverse=False, coset_gen=None):

@@ -41,6 +41,12 @@ struct CosetTables { void* lo; void* hi; int log_lo; };
 enum { TAG_MSM = 0, TAG_NTT, TAG_VEC, TAG_SPMV, TAG_SORT, TAG_ACC_G1, TAG_ACC_G2, TAG_REDUCE, TAG_COUNT };
 struct EvPair { hipEvent_t a, b; int tag; };
 
+// The fold of an MSM's partial sums on the host, by reduction kind:
+//   WINDOWS  classic per-window sums: Horner with c doublings per window            PLAIN  group sums of one shared bucket set: added
+//   BITS     per-bit sums T_k of a small shared bucket set: Horner with ONE doubling per step
+//   GRID     row / column bit sums of a large shared bucket set (k_msm_grid_*): (log_l + 1) gc column sums, then log_h gr row sums
+struct MsmFold { enum { WINDOWS = 0, PLAIN = 1, BITS = 2, GRID = 3 }; int kind = WINDOWS, c = 0, nsums = 0, log_l = 0, log_h = 0; uint32_t gc = 1, gr = 1; };
+
 struct MsmTicket {
     bool live = false;
     int curve = 0, group = 0, k = 0, c = 0, nwin = 0;
@@ -48,9 +54,7 @@ struct MsmTicket {
     uint32_t* h_flags = nullptr; bool optimistic = false;
     const cg_bases* bases = nullptr; size_t offset = 0, n = 0; std::vector<const void*> scalars;
     int nsums = 0;            // partial sums per component delivered by the GPU
-    bool plain_fold = false;  // true: add them (precomputed tables); false: Horner with c doublings (classic)
-    bool bit_fold = false;    // the sums are the per-bit sums T_k of a small shared bucket set: Horner with ONE doubling per step
-    bool grid_fold = false; int log_l = 0, log_h = 0; uint32_t gc = 1, gr = 1;   // row / column bit sums of a large shared bucket set (k_msm_grid_*)
+    MsmFold fold;             // how the host folds them (msm_fold_sums in capi_msm.hip)
     void* h_pinned = nullptr; size_t pinned_bytes = 0;   // k * nwin window sums (XYZZ)
     hipEvent_t done = nullptr;
 };

@@ -26,6 +26,39 @@ Jacobian<F> msm_fold_windows(const XYZZ<F>* w, int nwin, int c) {
     return xyzz_to_jacobian(acc);
 }
 
+// How the host folds the partial sums of one bucket-set reduction (msm_reduce_batch) into the MSM's result: by the reduction kind of the geometry.
+MsmFold msm_fold_rule(const MsmGeom& g, bool shared) {
+    MsmFold f;
+    f.kind = g.grid ? MsmFold::GRID : g.bitsum ? MsmFold::BITS : shared ? MsmFold::PLAIN : MsmFold::WINDOWS;
+    f.c = g.c; f.nsums = g.ngroups; f.log_l = g.log_l; f.log_h = g.log_h; f.gc = g.gc; f.gr = g.gr;
+    return f;
+}
+// The host's share of an MSM: ~100 point additions per result, on 64-bit limbs (host_ec64.hpp: the same bytes as the kernels' 32-bit limbs; 3x the
+// 32-bit host code, 0.2 ms less at the tail of a 2^22 proof, 0.5 ms per 2^16 proof).  One function for cg_msm_end and cg_msm_stages_dev.
+template <class F>
+cg64::Xyzz<F> msm_fold_sums(const cg64::Xyzz<F>* hs, const MsmFold& f) {
+    typedef cg64::Xyzz<F> X;
+    X acc;
+    if (f.kind == MsmFold::GRID) {
+        // sum_b (b + 1) B_b = sum_k 2^k TC_k + 2^log_l sum_k 2^k TR_k: bit sums of the column side (k <= log_l, gc partial sums each)
+        // then of the row side (k < log_h, gr each), merged into one sequence U_k and folded with one doubling per bit
+        std::vector<X> U((size_t)f.log_l + f.log_h + 1, X::inf());
+        size_t at = 0;
+        for (int kk = 0; kk <= f.log_l; kk++) for (uint32_t g = 0; g < f.gc; g++) U[kk] = cg64::add(U[kk], hs[at++]);
+        for (int kk = 0; kk < f.log_h; kk++) for (uint32_t g = 0; g < f.gr; g++) U[f.log_l + kk] = cg64::add(U[f.log_l + kk], hs[at++]);
+        acc = U.back();
+        for (size_t i = U.size() - 1; i-- > 0;) acc = cg64::add(cg64::dbl(acc), U[i]);
+    } else if (f.kind == MsmFold::BITS) {                   // sum_k 2^k T_k
+        acc = hs[f.nsums - 1];
+        for (int i = f.nsums - 2; i >= 0; i--) acc = cg64::add(cg64::dbl(acc), hs[i]);
+    } else if (f.kind == MsmFold::PLAIN) { acc = hs[0]; for (int i = 1; i < f.nsums; i++) acc = cg64::add(acc, hs[i]); }
+    else {                                                  // classic windows: Horner with c doublings per window
+        acc = hs[f.nsums - 1];
+        for (int i = f.nsums - 2; i >= 0; i--) { for (int d = 0; d < f.c; d++) acc = cg64::dbl(acc); acc = cg64::add(acc, hs[i]); }
+    }
+    return acc;
+}
+
 int ticket_slot(cg_ctx* ctx) {
     for (size_t i = 0; i < ctx->tickets.size(); i++) if (!ctx->tickets[i].live) return (int)i;
     ctx->tickets.emplace_back();
@@ -173,8 +206,7 @@ int msm_begin_multi_impl_(cg_ctx* ctx, int nb, const cg_bases* const* bases, con
         slots[b] = ticket_slot(ctx);
         MsmTicket& t = ctx->tickets[slots[b]];
         t.live = true;   // reserve before asking for the next slot
-        t.curve = curve; t.group = bases[b]->group; t.k = k; t.c = c; t.nwin = nwin; t.nsums = nsums; t.plain_fold = shared && !geom.bitsum && !geom.grid; t.bit_fold = geom.bitsum;
-        t.grid_fold = geom.grid; t.log_l = geom.log_l; t.log_h = geom.log_h; t.gc = geom.gc; t.gr = geom.gr;
+        t.curve = curve; t.group = bases[b]->group; t.k = k; t.c = c; t.nwin = nwin; t.nsums = nsums; t.fold = msm_fold_rule(geom, shared);
         t.optimistic = cap != 0; t.bases = bases[b]; t.offset = offsets ? offsets[b] : 0; t.n = n; t.scalars.assign(d_scalars, d_scalars + (n ? k : 0));
         if (!t.h_flags) HIPCHK(hipHostMalloc((void**)&t.h_flags, 8 * sizeof(uint32_t), hipHostMallocDefault));
         for (int i = 0; i < 8; i++) t.h_flags[i] = 0;
@@ -188,7 +220,7 @@ int msm_begin_multi_impl_(cg_ctx* ctx, int nb, const cg_bases* const* bases, con
                 t.pinned_bytes = need;
             }
             if (n == 0) { XYZZ<F>* h = (XYZZ<F>*)t.h_pinned; for (int i = 0; i < k * nsums; i++) h[i] = XYZZ<F>::infinity(); }
-            else acc_bytes = std::max(acc_bytes, msm_acc_scratch_bytes<F>(n, c, nwin, shared, chunk_request));
+            else acc_bytes = std::max(acc_bytes, msm_acc_scratch_bytes<F>(msm_geom_of<F>(n, c, nwin, shared, chunk_request)));
             return 0;
         });
         if (rc) return rc;
@@ -289,7 +321,7 @@ int msm_begin_multi_impl_(cg_ctx* ctx, int nb, const cg_bases* const* bases, con
             for (const PendSet& ps : pd) { sets.push_back(ps.set); if (!solo && !seen[ps.sched]) { seen[ps.sched] = true; evm[nm++] = ctx->ev_merged[rs][ps.sched]; } }
             int rc = with_coord_field(curve, gi == 0 ? CG_G1 : CG_G2, [&](auto ftag) -> int {
                 typedef decltype(ftag) F;
-                return msm_reduce_batch<F>(rst, sets.data(), (int)sets.size(), n, c, nwin, shared, sps[pd[0].comp].cap, evm, nm, pev, chunk_request);
+                return msm_reduce_batch<F>(rst, sets.data(), (int)sets.size(), msm_geom_of<F>(n, c, nwin, shared, chunk_request), sps[pd[0].comp].cap, evm, nm, pev);
             });
             if (rc) return rc;
             if (!solo) for (const PendSet& ps : pd) {
@@ -344,7 +376,7 @@ int msm_begin_multi_impl_(cg_ctx* ctx, int nb, const cg_bases* const* bases, con
                 if (ctx->stats_on) { const int i1 = ev_open(ctx, gi == 0 ? TAG_ACC_G1 : TAG_ACC_G2); evs[0] = ctx->ev_live[i1].a; evs[1] = ctx->ev_live[i1].b; pev = evs; }
                 int rc = with_coord_field(curve, gi == 0 ? CG_G1 : CG_G2, [&](auto ftag) -> int {
                     typedef decltype(ftag) F;
-                    return msm_accumulate_batch<F>(acc_stream[gi], sets.data(), (int)sets.size(), n, c, nwin, shared, sps[0].cap, pev, chunk_request, false);
+                    return msm_accumulate_batch<F>(acc_stream[gi], sets.data(), (int)sets.size(), msm_geom_of<F>(n, c, nwin, shared, chunk_request), sps[0].cap, pev, false);
                 });
                 if (rc) return rc;
                 if (gi == 0 && !solo) HIPCHK(hipStreamWaitEvent(sortst, ctx->ev_sorted[k - 1], 0));     // (the sort stream has nothing else left in this call)
@@ -374,7 +406,7 @@ int msm_begin_multi_impl_(cg_ctx* ctx, int nb, const cg_bases* const* bases, con
             const MsmAccSet as = acc_set(b, j, scratch);
             int rc = with_coord_field(curve, t.group, [&](auto ftag) -> int {
                 typedef decltype(ftag) F;
-                return msm_accumulate_batch<F>(ctx->stream, &as, 1, n, c, nwin, shared, sp.cap, pev, chunk_request, ctx->g2_slices != 0);
+                return msm_accumulate_batch<F>(ctx->stream, &as, 1, msm_geom_of<F>(n, c, nwin, shared, chunk_request), sp.cap, pev, ctx->g2_slices != 0);
             });
             if (rc) return rc;
             pend[gi].push_back(PendSet{red_set(b, j, scratch), slot, j % nsched, b, j});
@@ -457,30 +489,10 @@ int msm_end_impl(cg_ctx* ctx, int ticket, void* h_out) {
     // the same bytes as the kernels' 32-bit limbs; 3x the 32-bit host code, 0.2 ms less at the tail of a 2^22 proof, 0.5 ms per 2^16 proof)
     return with_group64(t.curve, t.group, [&](auto ftag, auto) -> int {
         typedef decltype(ftag) F;
-        typedef cg64::Xyzz<F> X;
-        const X* h = (const X*)t.h_pinned;
+        const cg64::Xyzz<F>* h = (const cg64::Xyzz<F>*)t.h_pinned;
         cg64::Jac<F>* out = (cg64::Jac<F>*)h_out;
         for (int j = 0; j < t.k; j++) {
-            const X* hs = h + (size_t)j * t.nsums;
-            X acc;
-            if (t.grid_fold) {
-                // sum_b (b + 1) B_b = sum_k 2^k TC_k + 2^log_l sum_k 2^k TR_k: bit sums of the column side (k <= log_l, gc partial sums each)
-                // then of the row side (k < log_h, gr each), merged into one sequence U_k and folded with one doubling per bit
-                std::vector<X> U((size_t)t.log_l + t.log_h + 1, X::inf());
-                size_t at = 0;
-                for (int kk = 0; kk <= t.log_l; kk++) for (uint32_t g = 0; g < t.gc; g++) U[kk] = cg64::add(U[kk], hs[at++]);
-                for (int kk = 0; kk < t.log_h; kk++) for (uint32_t g = 0; g < t.gr; g++) U[t.log_l + kk] = cg64::add(U[t.log_l + kk], hs[at++]);
-                acc = U.back();
-                for (size_t i = U.size() - 1; i-- > 0;) acc = cg64::add(cg64::dbl(acc), U[i]);
-            } else if (t.bit_fold) {                            // sum_k 2^k T_k
-                acc = hs[t.nsums - 1];
-                for (int i = t.nsums - 2; i >= 0; i--) acc = cg64::add(cg64::dbl(acc), hs[i]);
-            } else if (t.plain_fold) { acc = hs[0]; for (int i = 1; i < t.nsums; i++) acc = cg64::add(acc, hs[i]); }
-            else {                                              // classic windows: Horner with c doublings per window
-                acc = hs[t.nsums - 1];
-                for (int i = t.nsums - 2; i >= 0; i--) { for (int d = 0; d < t.c; d++) acc = cg64::dbl(acc); acc = cg64::add(acc, hs[i]); }
-            }
-            const cg64::Jac<F> r = cg64::to_jac(acc);
+            const cg64::Jac<F> r = cg64::to_jac(msm_fold_sums<F>(h + (size_t)j * t.nsums, t.fold));
             memcpy(out + j, &r, sizeof r);
         }
         return 0;
@@ -591,6 +603,141 @@ int32_t cg_msm_schedule_dev(cg_ctx* ctx, int32_t curve, const void* d_scalars, s
     if (rc) return rc;
     HIPCHK(e);
     *path_taken = sp.path; *overflow = ov;
+    return 0;
+}
+
+// The point side alone (see the header): msm_accumulate_batch and msm_reduce_batch, the launchers an MSM call uses, over hand-built schedules and
+// an explicit chunk length, with the state between the stages brought down.  Nothing of the context's MSM state is touched: the scratch is the
+// entry's own, pre-filled with 0xFF bytes so that what no kernel wrote is recognisable, and everything runs on the main stream.
+//  * Every index a kernel will read is checked on the host first (the table's rows, the window field, the scan, the total), so no schedule a
+//    test builds can make a kernel read outside the table, the list or the scratch.
+//  * k_msm_accumulate_pf reads the index list in 16-byte quads from a 16-byte boundary and so up to 12 bytes past the last entry.  In an MSM
+//    call `sorted` is one `take` of the sort scratch (fr_impl.hpp): it starts on a 256-byte boundary of a hipMalloc'ed arena and its region is
+//    rounded up to 256 bytes, so the quad that holds the last entry ends inside the region.  The copy here has the same two properties: a
+//    hipMalloc'ed block of align_up(entries * 4) bytes.
+//  * The sets' scratch slots lie one slot apart in DESCENDING order, so that msm_accumulate_batch clears each set's buckets by itself; its one
+//    fill over ascending neighbouring slots would also clear the continuation pieces in between, and an unwritten piece would read as infinity.
+//  * The table is used as registered: a table with a compacted copy (many points at infinity) is NOT replaced by it as in an MSM call.
+int32_t cg_msm_stages_dev(cg_ctx* ctx, const cg_bases* bases, int32_t c, size_t entries, uint32_t chunk_len, uint32_t cap, int32_t nsets,
+                          const uint32_t* const* h_counts, const uint32_t* const* h_offsets, const uint32_t* const* h_sorted,
+                          void* h_acc_buckets, void* h_acc_cont, uint32_t* h_cont_state, uint32_t* h_cont_bucket, void* h_merged_buckets,
+                          void* h_partials, void* h_folded, uint32_t* h_geom) {
+    if (!ctx || !bases || !h_counts || !h_offsets || !h_sorted) return fail(CG_ERR_ARG, "null argument");
+    if (bases->device != ctx->device) return fail(CG_ERR_ARG, "bases live on another device");
+    if (nsets < 1 || nsets > std::min(ACC_MAX_SETS, RED_MAX_SETS)) return fail(CG_ERR_ARG, "cg_msm_stages_dev: 1 .. 8 sets");
+    for (int s = 0; s < nsets; s++) if (!h_counts[s] || !h_offsets[s] || !h_sorted[s]) return fail(CG_ERR_ARG, "null argument");
+    if ((h_acc_cont == nullptr) != (h_cont_state == nullptr)) return fail(CG_ERR_ARG, "cg_msm_stages_dev: the continuation pieces come with their states");
+    const bool shared = bases->pre_c != 0;
+    if (shared ? c != bases->pre_c : (c < 2 || c > 20)) return fail(CG_ERR_ARG, "cg_msm_stages_dev: window size out of range (the table's window when it is precomputed, else 2 .. 20)");
+    if (chunk_len < 1) return fail(CG_ERR_ARG, "cg_msm_stages_dev: chunk length below 1");
+    if (entries < 1 || entries >= ((uint64_t)1 << 32)) return fail(CG_ERR_ARG, "cg_msm_stages_dev: schedule positions are 32-bit, and there is at least one");
+    if (((uint64_t)entries + chunk_len - 1) / chunk_len >= ((uint64_t)1 << 32)) return fail(CG_ERR_ARG, "cg_msm_stages_dev: chunk count does not fit 32 bits");
+    int bits = 0;
+    { int rc = with_fr(bases->curve, [&](auto tag) -> int { bits = decltype(tag)::Params::BITS; return 0; }); if (rc) return rc; }
+    const int nwin = bits / c + 1;
+    if (shared && nwin != bases->pre_nwin) return fail(CG_ERR_ARG, "internal: window count mismatch");
+    const size_t rows = bases->n, nbuckets = (size_t)(shared ? 1 : nwin) << (c - 1);
+    if (cap && (uint64_t)nbuckets * cap >= ((uint64_t)1 << 32)) return fail(CG_ERR_ARG, "cg_msm_stages_dev: the padded list takes cap < 2^32 / buckets");
+    std::vector<size_t> totals(nsets);
+    for (int s = 0; s < nsets; s++) {
+        uint64_t run = 0;
+        for (size_t b = 0; b < nbuckets; b++) {
+            if (h_offsets[s][b] != run) return fail(CG_ERR_ARG, "cg_msm_stages_dev: offsets are not the exclusive scan of the counts (of min(count, cap) in the padded layout)");
+            run += cap ? std::min(h_counts[s][b], cap) : h_counts[s][b];
+            if (run > entries) return fail(CG_ERR_ARG, "cg_msm_stages_dev: the schedule holds more than `entries` entries");
+        }
+        totals[s] = (size_t)run;
+        auto entry_ok = [&](uint32_t e) -> int {
+            if (shared) {
+                if ((e & 0xffffffu) >= rows) return fail(CG_ERR_ARG, "cg_msm_stages_dev: point index outside the table");
+                if ((int)((e >> 24) & 0x7fu) >= nwin) return fail(CG_ERR_ARG, "cg_msm_stages_dev: window field outside the table's windows");
+            } else if ((e & 0x7fffffffu) >= rows) return fail(CG_ERR_ARG, "cg_msm_stages_dev: point index outside the table");
+            return 0;
+        };
+        if (cap) { for (size_t b = 0; b < nbuckets; b++) for (uint32_t k = 0; k < std::min(h_counts[s][b], cap); k++) if (int rc = entry_ok(h_sorted[s][b * cap + k])) return rc; }
+        else for (size_t i = 0; i < totals[s]; i++) if (int rc = entry_ok(h_sorted[s][i])) return rc;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    const hipStream_t st = ctx->stream;
+    const size_t jac = bases->pt_bytes / 2 * 3;
+    std::vector<void*> blocks; void* h_sums = nullptr;
+    auto dev = [&](void** p, size_t bytes) -> int { HIPCHK(hip_malloc_flush(p, std::max<size_t>(bytes, 256))); blocks.push_back(*p); return 0; };
+    MsmGeom g{};
+    int rc = with_coord_field(bases->curve, bases->group, [&](auto ftag) -> int {
+        typedef decltype(ftag) F;
+        static_assert(sizeof(Affine<F>) * 2 == sizeof(XYZZ<F>), "");
+        g = msm_geom_with_chunks(msm_geom_of<F>(std::max<size_t>(entries / nwin, 1), c, nwin, shared, 0), entries, chunk_len);
+        const size_t slot = align_up(msm_acc_scratch_bytes<F>(g));
+        const size_t sorted_bytes = cap ? align_up(nbuckets * cap * 4) : align_up(entries * 4), nb_bytes = align_up(nbuckets * 4);
+        const size_t dbg = std::max<size_t>(nbuckets, g.nchunks);
+        char* scratch = nullptr; char* sched = nullptr; Affine<F>* d_aff = nullptr; uint32_t* d_state = nullptr;
+        if (int r = dev((void**)&scratch, (size_t)nsets * slot)) return r;
+        if (int r = dev((void**)&sched, (size_t)nsets * (sorted_bytes + 2 * nb_bytes))) return r;
+        if (int r = dev((void**)&d_aff, dbg * sizeof(Affine<F>))) return r;
+        if (int r = dev((void**)&d_state, dbg * 4)) return r;
+        HIPCHK(hipHostMalloc(&h_sums, std::max<size_t>((size_t)nsets * g.ngroups * sizeof(XYZZ<F>), 256), hipHostMallocDefault));
+        HIPCHK(hipMemsetAsync(scratch, 0xFF, (size_t)nsets * slot, st));
+        HIPCHK(hipMemsetAsync(sched, 0xFF, (size_t)nsets * (sorted_bytes + 2 * nb_bytes), st));
+        memset(h_sums, 0xFF, (size_t)nsets * g.ngroups * sizeof(XYZZ<F>));
+        MsmAccSet as[ACC_MAX_SETS]; MsmRedSet rs[RED_MAX_SETS]; MsmScratchView view[ACC_MAX_SETS];
+        for (int s = 0; s < nsets; s++) {
+            char* base = sched + (size_t)s * (sorted_bytes + 2 * nb_bytes);
+            uint32_t* d_sorted = (uint32_t*)base; uint32_t* d_counts = (uint32_t*)(base + sorted_bytes); uint32_t* d_offsets = (uint32_t*)(base + sorted_bytes + nb_bytes);
+            const size_t words = cap ? nbuckets * cap : totals[s];
+            if (words) HIPCHK(hipMemcpyAsync(d_sorted, h_sorted[s], words * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_counts, h_counts[s], nbuckets * 4, hipMemcpyHostToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_offsets, h_offsets[s], nbuckets * 4, hipMemcpyHostToDevice, st));
+            char* sl = scratch + (size_t)(nsets - 1 - s) * slot;
+            const char* pts = (const char*)(shared ? bases->d_pre : bases->d_pts);
+            as[s] = MsmAccSet{pts, shared ? bases->n : 0, d_sorted, d_offsets, d_counts, sl, !bases->no_inf};
+            rs[s] = MsmRedSet{sl, d_offsets, d_counts, (char*)h_sums + (size_t)s * g.ngroups * sizeof(XYZZ<F>)};
+            view[s] = msm_acc_scratch_view<F>(sl, g);
+        }
+        // limb-form points of every set -> packed affine records (and their states) on the host
+        auto bring_down = [&](bool cont, void* h_points, uint32_t* h_state) -> int {
+            const size_t cnt = cont ? g.nchunks : nbuckets;
+            for (int s = 0; s < nsets; s++) {
+                HIPCHK(hipMemsetAsync(d_aff, 0xFF, cnt * sizeof(Affine<F>), st));
+                if (int r = msm_debug_to_affine<F>(st, cont ? view[s].cont : view[s].buckets, cnt, d_aff, d_state)) return r;
+                HIPCHK(hipMemcpyAsync((char*)h_points + (size_t)s * cnt * sizeof(Affine<F>), d_aff, cnt * sizeof(Affine<F>), hipMemcpyDeviceToHost, st));
+                if (h_state) HIPCHK(hipMemcpyAsync(h_state + (size_t)s * cnt, d_state, cnt * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));            // d_aff / d_state serve the next set
+            }
+            return 0;
+        };
+        if (int r = msm_accumulate_batch<F>(st, as, nsets, g, cap, nullptr, ctx->g2_slices != 0)) return r;
+        if (h_acc_buckets) if (int r = bring_down(false, h_acc_buckets, nullptr)) return r;
+        if (h_acc_cont) if (int r = bring_down(true, h_acc_cont, h_cont_state)) return r;
+        if (h_cont_bucket) for (int s = 0; s < nsets; s++) HIPCHK(hipMemcpyAsync(h_cont_bucket + (size_t)s * g.nchunks, view[s].cont_bucket, (size_t)g.nchunks * 4, hipMemcpyDeviceToHost, st));
+        if (h_merged_buckets || h_partials || h_folded) {
+            if (int r = msm_reduce_batch<F>(st, rs, nsets, g, cap, nullptr, 0, nullptr)) return r;
+            if (h_merged_buckets) if (int r = bring_down(false, h_merged_buckets, nullptr)) return r;
+        }
+        return 0;
+    });
+    const hipError_t e = hipStreamSynchronize(st);
+    for (void* p : blocks) (void)hipFree(p);
+    if (!rc && e == hipSuccess && (h_partials || h_folded))
+        rc = with_group64(bases->curve, bases->group, [&](auto ftag, auto) -> int {
+            typedef decltype(ftag) F;
+            const cg64::Xyzz<F>* hs = (const cg64::Xyzz<F>*)h_sums;
+            const MsmFold fold = msm_fold_rule(g, shared);
+            for (int s = 0; s < nsets; s++) {
+                if (h_partials) for (int i = 0; i < g.ngroups; i++) { const cg64::Jac<F> r = cg64::to_jac(hs[(size_t)s * g.ngroups + i]); memcpy((char*)h_partials + ((size_t)s * g.ngroups + i) * jac, &r, sizeof r); }
+                if (h_folded) { const cg64::Jac<F> r = cg64::to_jac(msm_fold_sums<F>(hs + (size_t)s * g.ngroups, fold)); memcpy((char*)h_folded + (size_t)s * jac, &r, sizeof r); }
+            }
+            return 0;
+        });
+    if (h_sums) (void)hipHostFree(h_sums);
+    if (rc) return rc;
+    HIPCHK(e);
+    if (h_geom) {
+        uint32_t slice = 0;
+        (void)with_coord_field(bases->curve, bases->group, [&](auto ftag) -> int { slice = msm_acc_slice_groups<decltype(ftag)>(); return 0; });
+        const uint32_t rec[CG_MSM_GEOM_WORDS] = {g.grid ? (uint32_t)CG_MSM_REDUCE_GRID : g.bitsum ? (uint32_t)CG_MSM_REDUCE_BITSUM : (uint32_t)CG_MSM_REDUCE_SEGMENTS, (uint32_t)g.ngroups, g.nchunks, g.nb,
+                                                 (uint32_t)g.nsets, g.seg_len, g.segs, g.group_segs, g.bit_groups, (uint32_t)g.log_l, (uint32_t)g.log_h, g.gc, g.gr, g.chunk_len, slice, (uint32_t)nwin};
+        memcpy(h_geom, rec, sizeof rec);
+    }
     return 0;
 }
 

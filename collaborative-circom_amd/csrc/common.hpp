@@ -78,6 +78,7 @@ constexpr int BITSUM_ITEMS = 8;   // buckets per lane in k_msm_bitsum_partial
 #endif
 constexpr int GRID_LOG_L = 10, GRID_TR = CG_GRID_TR, GRID_TC = 64;   // k_msm_grid_partial: columns of the bucket grid, tile rows / columns per workgroup
 struct MsmGeom {            // derived sizes shared by the host-side planner and the launchers
+    int c;                  // window size
     uint32_t nb;            // buckets per bucket set = 2^(c-1)
     int nsets;              // bucket sets: nwin (classic) or 1 (shared: per-window precomputed tables)
     size_t nbuckets;        // nsets * nb
@@ -110,6 +111,7 @@ struct MsmRedSet { char* scratch; const uint32_t* offsets; const uint32_t* count
 // g2: coordinates in the quadratic extension (LDS accumulators, no lock-stepped residency): chunks capped at CG_G2_CHUNK.
 inline MsmGeom msm_geom(size_t n, int c, int nwin, bool shared, size_t resident_lanes = 0, uint32_t chunk_request = 0, bool g2 = false) {
     MsmGeom g;
+    g.c = c;
     g.nb = 1u << (c - 1);
     g.nsets = shared ? 1 : nwin;
     g.nbuckets = (size_t)g.nsets * g.nb;
@@ -149,6 +151,13 @@ inline MsmGeom msm_geom(size_t n, int c, int nwin, bool shared, size_t resident_
         g.chunk_len = (uint32_t)((entries + rounds * resident_lanes - 1) / (rounds * resident_lanes));   // between 2/3 and 3/2 of chunk_max (up to 192 entries): whole rounds matter more than the cap
     }
     g.nchunks = (uint32_t)std::max<size_t>(1, (entries + g.chunk_len - 1) / g.chunk_len);
+    return g;
+}
+// the same geometry with an explicit chunking (cg_msm_stages_dev): `chunk_len` entries per lane over a list of `entries`.  Scratch sizes, launch
+// sizes and kernels all follow from the one object (msm_acc_scratch_bytes, msm_accumulate_batch, msm_reduce_batch take it as an argument).
+inline MsmGeom msm_geom_with_chunks(MsmGeom g, size_t entries, uint32_t chunk_len) {
+    g.chunk_len = chunk_len;
+    g.nchunks = (uint32_t)std::max<size_t>(1, (entries + chunk_len - 1) / chunk_len);
     return g;
 }
 

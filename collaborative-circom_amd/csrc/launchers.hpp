@@ -49,10 +49,18 @@ template <class Fr> int msm_sort_direct_launch(hipStream_t st, const Fr* d_scala
                                                MsmSortPtrs* out, hipEvent_t* evs, int force = 0);
 
 // ---- group side of the MSM and the point kernels (msm_impl.hpp)
-template <class F> int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* evs, uint32_t chunk_request, bool g2_slices);
-template <class F> int msm_reduce_batch(hipStream_t st2, const MsmRedSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* ev_merged, int n_merged,
-                                        hipEvent_t* evs, uint32_t chunk_request);
-template <class F> size_t msm_acc_scratch_bytes(size_t n, int c, int nwin, bool shared, uint32_t chunk_request);
+// The geometry is computed ONCE per call (msm_geom_of: what an MSM call over n points uses; msm_geom_with_chunks: an explicit chunking) and handed
+// to everything that sizes scratch or launches from it.
+template <class F> MsmGeom msm_geom_of(size_t n, int c, int nwin, bool shared, uint32_t chunk_request);
+template <class F> int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, const MsmGeom& g, uint32_t cap, hipEvent_t* evs, bool g2_slices);
+template <class F> int msm_reduce_batch(hipStream_t st2, const MsmRedSet* sets, int nsets, const MsmGeom& g, uint32_t cap, hipEvent_t* ev_merged, int n_merged, hipEvent_t* evs);
+template <class F> size_t msm_acc_scratch_bytes(const MsmGeom& g);
+// cg_msm_stages_dev: the arrays of a scratch slot, the slice of a sliced accumulation, and limb-form points brought to packed affine records
+// (msm_debug_kernels.hpp: state[i] = 0 point, 1 infinity, 2 = the slot still holds the 0xFF bytes it was filled with; such a slot's record is left alone)
+struct MsmScratchView { void* buckets; void* cont; uint32_t* cont_bucket; size_t bucket_bytes; };
+template <class F> MsmScratchView msm_acc_scratch_view(char* scratch, const MsmGeom& g);
+template <class F> uint32_t msm_acc_slice_groups();
+template <class F> int msm_debug_to_affine(hipStream_t st, const void* d_limb_points, size_t n, Affine<F>* d_out, uint32_t* d_state);
 template <class F> int precompute_window_launch(hipStream_t st, const Affine<F>* d_src, Affine<F>* d_dst, size_t n, int c);
 template <class F> int check_on_curve_launch(hipStream_t st, const Affine<F>* d_pts, size_t n, const F& b, unsigned long long* d_counters);
 template <class F, class Fr> int check_subgroup_launch(hipStream_t st, const Affine<F>* d_pts, size_t n, unsigned long long* d_counters);

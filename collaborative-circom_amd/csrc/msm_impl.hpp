@@ -49,8 +49,18 @@ struct AccScratch {
     }
 };
 template <class F>
-size_t msm_acc_scratch_bytes(size_t n, int c, int nwin, bool shared, uint32_t chunk_request) {
-    return AccScratch<F>(nullptr, msm_geom_of<F>(n, c, nwin, shared, chunk_request)).bytes;
+size_t msm_acc_scratch_bytes(const MsmGeom& g) { return AccScratch<F>(nullptr, g).bytes; }
+// where a bucket set's arrays lie in its scratch slot (cg_msm_stages_dev downloads them)
+template <class F>
+MsmScratchView msm_acc_scratch_view(char* scratch, const MsmGeom& g) {
+    const AccScratch<F> sc(scratch, g);
+    return MsmScratchView{sc.buckets, sc.cont, sc.cont_bucket, sizeof(typename BucketOf<F>::type)};
+}
+// workgroups of one slice of a sliced G2 accumulation (CG_OPT_MSM_G2_SLICES): one chip-load by the LDS a workgroup holds; 0 = the field's launches are never sliced
+template <class F>
+uint32_t msm_acc_slice_groups() {
+    if constexpr (!IsFp2<F>::value) return 0;
+    else return 256u * (uint32_t)std::max<size_t>(1, ((size_t)160 << 10) / ((size_t)128 * 4 * sizeof(typename LazyOf<F>::type)));
 }
 
 // Bucket accumulation of UP TO ACC_MAX_SETS (bases, sorted schedule) pairs of one coordinate field and one launch geometry, each into
@@ -58,9 +68,8 @@ size_t msm_acc_scratch_bytes(size_t n, int c, int nwin, bool shared, uint32_t ch
 // itself; the tables and components of a small call go side by side).  table_stride != 0 selects the shared-bucket-set mode (bases =
 // window-0 table of a [nwin][table_stride] precomputed block).  evs (optional, 2 events) bracket the accumulation KERNEL(s) alone.
 template <class F>
-int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* evs, uint32_t chunk_request, bool g2_slices) {
+int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, const MsmGeom& g, uint32_t cap, hipEvent_t* evs, bool g2_slices) {
     if (nsets < 1 || nsets > ACC_MAX_SETS) return fail(CG_ERR_ARG, "internal: accumulation batch size");
-    const MsmGeom g = msm_geom_of<F>(n, c, nwin, shared, chunk_request);
     typedef typename BucketOf<F>::type B;                 // limb-form points (XYZZL)
     AccSets<F> S{};
     for (int i = 0; i < nsets; i++) {
@@ -94,7 +103,7 @@ int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_
     auto launch_pf = [&](auto kern, int T, size_t lds) -> int {
         if (lds > 0) { if (int rc = ensure_dynamic_lds((const void*)kern, lds)) return rc; }   // once per (kernel, device), not per launch
         const uint32_t groups = (g.nchunks + T - 1) / T;
-        const uint32_t slice = lds > 0 && g2_slices ? 256u * (uint32_t)std::max<size_t>(1, ((size_t)160 << 10) / lds) : groups;
+        const uint32_t slice = lds > 0 && g2_slices ? msm_acc_slice_groups<F>() : groups;
         for (uint32_t first = 0; first < groups; first += slice)
             hipLaunchKernelGGL(kern, dim3(std::min(slice, groups - first), (unsigned)nsets), dim3(T), lds, st, S, (uint32_t)g.nbuckets, g.chunk_len, g.nchunks, first * (uint32_t)T);
         return 0;
@@ -122,10 +131,9 @@ int msm_accumulate_batch(hipStream_t st, const MsmAccSet* sets, int nsets, size_
 // the step their stand-alone duration, not their work: the sets of a call that share a field go through them together.
 // evs (optional, 2 events) bracket the whole batch.
 template <class F>
-int msm_reduce_batch(hipStream_t st2, const MsmRedSet* sets, int nsets, size_t n, int c, int nwin, bool shared, uint32_t cap, hipEvent_t* ev_merged, int n_merged,
-                     hipEvent_t* evs, uint32_t chunk_request) {
+int msm_reduce_batch(hipStream_t st2, const MsmRedSet* sets, int nsets, const MsmGeom& g, uint32_t cap, hipEvent_t* ev_merged, int n_merged, hipEvent_t* evs) {
     if (nsets < 1 || nsets > RED_MAX_SETS) return fail(CG_ERR_ARG, "internal: reduction batch size");
-    const MsmGeom g = msm_geom_of<F>(n, c, nwin, shared, chunk_request);
+    const int c = g.c;
     typedef typename BucketOf<F>::type B;
     RedSets<B> S{};
     XYZZ<F>* wsums[RED_MAX_SETS];
@@ -262,6 +270,9 @@ int fixed_base_mul_launch(hipStream_t st, const Affine<F>& g, const Fr* d_scalar
     template decltype(msm_accumulate_batch<F>) msm_accumulate_batch<F>;                                                    \
     template decltype(msm_reduce_batch<F>) msm_reduce_batch<F>;                                                            \
     template decltype(msm_acc_scratch_bytes<F>) msm_acc_scratch_bytes<F>;                                                  \
+    template decltype(msm_geom_of<F>) msm_geom_of<F>;                                                                      \
+    template decltype(msm_acc_scratch_view<F>) msm_acc_scratch_view<F>;                                                    \
+    template decltype(msm_acc_slice_groups<F>) msm_acc_slice_groups<F>;                                                    \
     template decltype(precompute_window_launch<F>) precompute_window_launch<F>;                                            \
     template decltype(check_on_curve_launch<F>) check_on_curve_launch<F>;                                                  \
     template decltype(check_subgroup_launch<F, Fr>) check_subgroup_launch<F, Fr>;                                          \

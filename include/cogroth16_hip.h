@@ -263,6 +263,37 @@ int32_t cg_msm_set_scatter_capacity(cg_ctx* ctx, int32_t cap);
 enum { CG_MSM_PATH_GENERAL = 1, CG_MSM_PATH_SMALL = 2, CG_MSM_PATH_PARTITION = 3, CG_MSM_PATH_DIRECT = 4, CG_MSM_PATH_PARTITION_UNSTAGED = 5 };
 int32_t cg_msm_schedule_dev(cg_ctx* ctx, int32_t curve, const void* d_scalars, size_t n, int32_t c, int32_t shared, int32_t path, uint32_t cap,
                             uint32_t* h_counts, uint32_t* h_offsets, uint32_t* h_sorted, int32_t* path_taken, uint32_t* overflow);
+/* Diagnostic (tests, bring-up of a new device): the POINT side of the MSM alone, stage by stage, over schedules the caller builds.  Runs the
+ * launchers an MSM call uses for the bucket accumulation and for the merges and the reduction, over scratch of its own that is pre-filled with
+ * 0xFF bytes, and brings the state between the stages down.  The context's MSM state is not touched.  DESIGN.md §3 states the formats.
+ *   bases      a registered table; its state selects the mode as in an MSM call: precomputed with window c = ONE bucket set, entries carry the
+ *              window in bits 24-30 and index the [window][rows] block; otherwise one bucket set per window.  nbuckets = (sets) * 2^(c-1).
+ *              The table's infinity census is used as registered.  (A compacted copy of a sparse table is not substituted.)
+ *   c          the table's window when it is precomputed, else 2 .. 20
+ *   entries    what an MSM call passes as windows * points: the list length the chunks are laid over (>= every set's total, < 2^32)
+ *   chunk_len  entries per lane (>= 1); nchunks = ceil(entries / chunk_len)
+ *   cap        0 = compact list (h_sorted[s]: total words) and the pipelined accumulation kernel; > 0 = padded list (h_sorted[s]: nbuckets * cap words,
+ *              bucket b owns slots [b * cap, b * cap + min(count, cap))) and the plain kernel
+ *   nsets      1 .. 8 schedules of this one geometry, accumulated, merged and reduced together (blockIdx.y)
+ *   h_counts, h_offsets, h_sorted   per set, HOST arrays in the format of cg_msm_schedule_dev
+ * Refused with CG_ERR_ARG before anything is launched, the outputs untouched: offsets that are not the exclusive scan of the counts (of min(count,
+ * cap) when padded), a total above `entries`, a point index >= the table's rows, a window field >= the table's windows, a window size outside the mode's range.
+ * Outputs, each optional (NULL = not produced), set-major; points are packed affine records as in a table (infinity = all zero):
+ *   h_acc_buckets    [nsets][nbuckets] after the accumulation
+ *   h_acc_cont       [nsets][nchunks] continuation pieces, with h_cont_state (both or neither): 0 = point, 1 = infinity, 2 = never written (the
+ *                    record then holds 0xFF bytes)
+ *   h_cont_bucket    [nsets][nchunks] the pieces' tags as the accumulation left them
+ *   h_merged_buckets [nsets][nbuckets] after the three merge kernels
+ *   h_partials       [nsets][ngroups] the partial sums as the reduction hands them to the host, in its order, as Jacobian points (like the result of cg_msm_end)
+ *   h_folded         [nsets] the host's fold of each set's partial sums, Jacobian
+ *   h_geom           CG_MSM_GEOM_WORDS words: reduction kind (CG_MSM_REDUCE_*), ngroups, nchunks, nb (buckets per set), bucket sets, seg_len, segs, group_segs,
+ *                    bit_groups, log_l, log_h, gc, gr, chunk_len, workgroups per slice of a sliced accumulation (0: this field is never sliced), windows
+ * CG_OPT_MSM_G2_SLICES applies as in an MSM call.  Synchronises the stream. */
+enum { CG_MSM_REDUCE_SEGMENTS = 0, CG_MSM_REDUCE_BITSUM = 1, CG_MSM_REDUCE_GRID = 2, CG_MSM_GEOM_WORDS = 16 };
+int32_t cg_msm_stages_dev(cg_ctx* ctx, const cg_bases* bases, int32_t c, size_t entries, uint32_t chunk_len, uint32_t cap, int32_t nsets,
+                          const uint32_t* const* h_counts, const uint32_t* const* h_offsets, const uint32_t* const* h_sorted,
+                          void* h_acc_buckets, void* h_acc_cont, uint32_t* h_cont_state, uint32_t* h_cont_bucket, void* h_merged_buckets,
+                          void* h_partials, void* h_folded, uint32_t* h_geom);
 
 /* ---- FFTProvider::{fft,ifft}_in_place  (traits.rs:535-558; rep3.rs:893-921) ------------------------------------
  * k vectors of n = 2^j scalar-field elements, natural order in and out.  `h_group_gen` = domain.group_gen (the caller
