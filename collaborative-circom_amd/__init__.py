@@ -599,6 +599,11 @@ class Context:
     def vec_prefix_sum(self, curve, out, src, n): _chk(load().cg_vec_prefix_sum_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
     def vec_inverse(self, curve, out, src, n): _chk(load().cg_vec_inverse_dev(self.h, curve, _dp(out), _dp(src), C.c_size_t(n)))
 
+    def vec_check_canonical(self, curve, d_vec, n, d_count):
+        """cg_vec_check_canonical_dev: ADDS the number of the n elements of d_vec whose limbs are not below the modulus to the u64 in the 8-byte
+        device buffer d_count (the caller zeroes it); enqueued on the context's stream"""
+        _chk(load().cg_vec_check_canonical_dev(self.h, curve, _dp(d_vec), C.c_size_t(n), _dp(d_count)))
+
     def r1cs_check(self, curve, mats, n_rows, witness, result, nnz_total=0, form=0):
         """cg_r1cs_check_dev: mats = three (row_ptr, col, coeff) device triples (A, B, C); result = 16-byte device buffer (count, first failing row);
         form 0 = chosen by size, 1 = a lane per row triple, 2 = a wave per row triple"""

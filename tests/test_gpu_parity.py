@@ -692,7 +692,6 @@ def test_vec_prefix_product_inverse_affine(ctx, curve, n):
     for i in range(n):
         if x[i].any(): assert np.array_equal(prod[i], one)
         else: assert not inv[i].any()
-        if i > 64 and i % 97: continue                                 # spot check beyond the first elements
     if n <= 2049:
         np.testing.assert_array_equal(inv[5 % n], orc.field_inverse(curve, FR, x[5 % n]) if x[5 % n].any() else np.zeros(4, dtype=np.uint64))
     # inclusive prefix product, checked through the recurrence out[i] = out[i-1] * x[i] with oracle multiplications

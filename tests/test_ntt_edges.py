@@ -3,8 +3,10 @@
 The lazy kernels keep elements unreduced between stages; how far they grow depends on the limbs the kernels see, so the patterns below are set in
 those limbs (Montgomery representatives), where p - 1 is the largest value an input can hold.  The transform is linear over them, so the oracle,
 given the same limbs, is the reference as it stands.  Sizes: lg 3, 4, 6, 7, 8 (one pass: odd and even stage counts, the radix-2 step behind the
-radix-4 ones) and lg 11, 14, 16 (two passes, the first of 1, 4 and 6 stages under the default tile of 2^10).  One call transforms 8 vectors (the
-most a call takes), each with another pattern."""
+radix-4 ones), lg 11, 14, 16, 17 (two passes, the first of 1, 4, 6 and 7 stages under the default tile of 2^10; 7 + 10 at lg 17 is three radix-4
+steps and a radix-2 tail on a strided tile) and lg 18, the smallest three-pass plan, 4 + 4 + 10 stages: the only size here at which the middle
+passes run (k_ntt_ct_pass<F, false> with t > 0 and another pass behind it, k_ntt_dit_pass<F, false, false>).  One call transforms 8 vectors (the
+most a call takes), each with another pattern, at every size."""
 import numpy as np
 import pytest
 
@@ -14,7 +16,7 @@ from product import cg, ensure_built
 
 pytestmark = pytest.mark.gpu
 
-SIZES = (3, 4, 6, 7, 8, 11, 14, 16)
+SIZES = (3, 4, 6, 7, 8, 11, 14, 16, 17, 18)
 PATTERNS = ("all zero", "all p - 1", "p - 1 at index 0", "p - 1 at index n - 1", "alternating 0 / p - 1", "pure tone", "all >= p - 2^32", "uniform random")
 
 

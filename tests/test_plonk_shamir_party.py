@@ -14,6 +14,7 @@ import pytest
 import oracle_lib as orc
 from oracle_lib import BN254, BLS12_381, FR
 from product import cg, ensure_built
+from vec_ref import Mont, from_ints, to_ints
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CURVES = {"bn254": BN254, "bls12_381": BLS12_381}
@@ -366,37 +367,21 @@ def test_gpu_session_reuse_and_error_returns():
 
 
 # ---- GPU: the kernels alone, against Python integers ------------------------------------------------------------------------------------
-def to_ints(a):
-    a = np.ascontiguousarray(a, dtype=np.uint64).reshape(-1, 4)
-    return [int.from_bytes(row.tobytes(), "little") for row in a]
-
-
-def from_ints(v):
-    return np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in v), dtype=np.uint64).reshape(-1, 4).copy()
-
-
-class Mont:
-    """Montgomery representatives (x R mod r, R = 2^256) as Python integers"""
-
-    def __init__(self, curve):
-        self.r = orc.MODULI[(curve, FR)]; self.R = (1 << 256) % self.r; self.Rinv = pow(self.R, -1, self.r)
-
-    def mul(self, a, b): return a * b * self.Rinv % self.r
-    def of(self, x): return x * self.R % self.r
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("curve_name", ["bn254", "bls12_381"])
-@pytest.mark.parametrize("degree", [1, 2, 4])
-@pytest.mark.parametrize("parties", [3, 5, 7])
+@pytest.mark.parametrize("degree,parties", [pytest.param(d, n, id=f"{n}-{d}") for n in (3, 5, 7) for d in (1, 2, 4)] +
+                         [pytest.param(d, n, id=f"{n}-{d}") for d, n in ((0, 3), (5, 3), (5, 7), (6, 5), (9, 19))])
 def test_gpu_shamir_share_kernel_equals_horner_in_python_integers(curve_name, degree, parties):
+    """degrees 1, 2, 4 stay in k_shamir_share's registers (SHARE_REG_DEGREE = 4); 5 is the first that re-reads its coefficients per receiver,
+    6 and 9 (19 receivers) go on from there; degree 0 copies the secrets.  The reference is quadratic in the degree, so 2^16 + 3 elements run
+    on the register path only."""
     ensure_built()
     curve = CURVES[curve_name]; F = Mont(curve)
     ctx = cg.Context(0)
     rng = np.random.default_rng(1000 * degree + parties)
     coeff_off, coeff_stride, out_off, out_stride = 3, degree + 2, 1, 2
     try:
-        for ln in (1, 63, 64, 65, 1000, (1 << 16) + 3):
+        for ln in (1, 63, 64, 65, 1000, (1 << 16) + 3) if degree in (1, 2, 4) else (1, 65, 1000):
             sec = orc.random_field(curve, FR, ln, rng)
             for j, v in enumerate((0, 1, F.r - 1, F.R)[:ln]): sec[j] = from_ints([v])[0]
             co = orc.random_field(curve, FR, coeff_off + ln * coeff_stride, rng)
@@ -416,7 +401,7 @@ def test_gpu_shamir_share_kernel_equals_horner_in_python_integers(curve_name, de
             for b in outs + [d_sec, d_co]: b.free()
         # the king's layout: the party's own share written over the secrets
         ln = 1000
-        sec = orc.random_field(curve, FR, ln, rng); co = orc.random_field(curve, FR, ln * degree, rng)
+        sec = orc.random_field(curve, FR, ln, rng); co = orc.random_field(curve, FR, max(1, ln * degree), rng)
         d_sec, d_co = ctx.to_device(sec), ctx.to_device(co)
         outs = [d_sec] + [ctx.alloc(ln * 32) for _ in range(parties - 1)]
         ctx.shamir_share(curve, d_sec, d_co, 0, degree, ln, degree, outs)
